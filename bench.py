@@ -12,7 +12,9 @@ also runs that pool alone so the line carries the single-GPU rate it is to be co
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the
 round kernel, `cpu_baseline` (the C oracle timed on a bounded sample of the same workload) and `compression_cost`
-(what the default chain count costs in compressed size, real BSC).
+(what the default chain count costs in compressed size, real BSC).  --dump-outputs DIR writes what the last timed step
+computed (its output streams, sampled to at most 64 MB) for output-for-output comparison of two builds; that step's
+stage is freed after the timer stops instead of inside the step.
 """
 import argparse
 import ctypes as C
@@ -28,6 +30,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec peak
 RANDOM_REQ_PEAK_G = 49.0  # measured: independent random <=32-byte reads, tables >= 4 GiB (tools/random_gather_bench.hip)
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this many bytes in all (.npy headers included)
 
 
 def parse():
@@ -63,7 +66,36 @@ def parse():
                     help="reads in the pools of compression_cost.output_changing_choices (0 = skip)")
     ap.add_argument("--files-sample", type=int, default=100_000_000,
                     help="reads in the file-contract leg (stage_incl_files): the whole workload by default; 0 = skip")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the streams the last timed step computed as DIR/<name>.npy "
+                         "(float64; a fixed, seeded sample of the longer streams, %d MB in all)" % (DUMP_BYTES // 10**6))
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.force_pool or (int(os.environ.get("WORLD_SIZE", "1")) > 1 and not a.lanes)):
+        ap.error("--dump-outputs covers the single-GPU and --lanes runs, not the shared pool")
+    return a
+
+
+def dump_outputs(d, res, seed=20240601):
+    """--dump-outputs: every array of `res` (ReorderStage.streams()) as d/<name>.npy in float64, exact for the integers
+    the streams hold (< 2**53).  An array longer than its share of DUMP_BYTES is represented by a sample at sorted
+    positions drawn by a generator seeded with `seed` from the array's length alone: the same positions in every run of
+    the same arguments, and the same positions in every stream of the same length (order, rc, flag, pos, rlen line up)."""
+    os.makedirs(d, exist_ok=True)
+    arrs = sorted(((k, v) for k, v in res.items() if isinstance(v, np.ndarray)), key=lambda kv: (kv[1].size, kv[0]))
+    left = DUMP_BYTES // 8 - 32 * len(arrs)  # (elements; 256 bytes of .npy header per file kept aside)
+    written = {}
+    for i, (k, v) in enumerate(arrs):
+        if i == 0 or v.size != arrs[i - 1][1].size:  # the shorter arrays go first and whole; the rest share what remains
+            m = min(v.size, left // (len(arrs) - i))
+        x = v.reshape(-1)
+        if m < x.size:
+            x = x[np.sort(np.random.default_rng(seed).choice(x.size, m, replace=False))]
+        np.save(os.path.join(d, k + ".npy"), x.astype(np.float64))
+        left -= m
+        written[k] = (int(v.size), int(m))
+    return written
 
 
 def algorithmic_bytes_search(st, W):
@@ -426,15 +458,31 @@ def main():
     assert rc == 0, L_.spring_reorder_last_error()
     torch.cuda.synchronize()
 
-    def one_pass(**kw):
+    kept = []  # --dump-outputs: the stage of the last timed step, open until its streams are read after the timer stops
+
+    def one_pass(keep=False, **kw):
         s = spring_amd.ReorderStage(spring_amd.ReorderOpts(device=dev, num_chains=a.chains, num_thr=a.num_thr, **kw))
         s.load_dna_device(buf.data_ptr(), nb, n, L, True)
         s.run()
         st = s.stats()
-        s.close()
+        if keep:
+            kept.append(s)
+        else:
+            s.close()
         return st
 
-    el, st = lanes.timed_steps(one_pass, a.steps, a.warmup)
+    passes = [0]
+
+    def timed_pass():
+        passes[0] += 1
+        return one_pass(keep=bool(a.dump_outputs) and rank == 0 and passes[0] == max(a.warmup, 0) + a.steps)  # (rank 0's lane)
+
+    el, st = lanes.timed_steps(timed_pass, a.steps, a.warmup)
+    if kept:
+        written = dump_outputs(a.dump_outputs, kept[0].streams())
+        kept.pop().close()
+        print("# --dump-outputs %s: %s" % (a.dump_outputs, ", ".join("%s %d of %d" % (k, m, sz) for k, (sz, m) in written.items())),
+              file=sys.stderr, flush=True)
     out = headline_line(a, world, el, st, G)
 
     if rank == 0 and world == 1 and not a.no_roofline:

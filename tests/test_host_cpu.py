@@ -108,6 +108,35 @@ def test_bench_line_builders_keep_the_contract():
     assert 0 < r["frac"] < 1 and r["traffic"] > r["algorithmic_bytes_per_launch"]
 
 
+def test_bench_dump_outputs_fixed_sample_within_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 files, within the byte budget, short arrays whole, long ones sampled at the same
+    sorted positions in every run and in every stream of the same length; --steps 0 is refused."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 400_000)
+    nm, ns = 50_000, 7_000
+    res = dict(order=np.arange(nm, dtype=np.uint32), rc=(np.arange(nm) % 2).astype(np.uint8), pos=np.arange(nm) * 3,
+               order_s=np.arange(ns, dtype=np.uint32), tid_off=np.array([0, 20_000, nm], np.uint64), stats={"rounds": 1})
+    got = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), res)
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 400_000
+        got.append({f.name: np.load(f) for f in d.iterdir()})
+    assert sorted(got[0]) == ["order.npy", "order_s.npy", "pos.npy", "rc.npy", "tid_off.npy"]
+    for k, v in got[0].items():
+        assert v.dtype == np.float64 and np.array_equal(v, got[1][k]), k
+    assert np.array_equal(got[0]["tid_off.npy"], [0, 20_000, nm])
+    o = got[0]["order.npy"]  # = the sampled positions
+    assert 0 < o.size < nm and np.all(np.diff(o) > 0) and o[-1] < nm
+    assert np.array_equal(got[0]["rc.npy"], o % 2) and np.array_equal(got[0]["pos.npy"], o * 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
 def test_ctypes_mirrors_match_the_c_header(tmp_path):
     """spring_amd/_lib.py mirrors spring_reorder_opts / spring_reorder_stats by hand: sizes and the offsets of the
     fields added last must equal what a C compiler makes of include/spring_reorder.h."""
