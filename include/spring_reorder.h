@@ -90,7 +90,9 @@ typedef struct {
                              pool from the top, reorder.h:576-599).  THE OUTPUT DEPENDS ON IT for num_chains > 1.  <= 0: the
                              library's choice, reported in stats.phases, the same on one GPU and in a pool.  2 needs the fused
                              round, >= 4096 chains, 8192 .. 2^31 - 1 reads, not fewer reads than chains; in a pool over G GPUs
-                             both groups' chain counts must be multiples of 256 G */
+                             both groups' chain counts must be multiples of 256 G.  The library's choice is 2 only where
+                             num_chains is a multiple of 2048 (and >= 16 384 on shallow pools): other counts run one group,
+                             on one GPU as in a pool, so that the choice never depends on the number of ranks */
   int32_t known_absent;   /* four-chain round kernel, reads up to 192 bases: chains remember which windows of their consensus
                              are known absent from the dictionaries and skip them (the table is immutable).  0 = on, -1 = off */
 } spring_reorder_opts;
@@ -202,24 +204,41 @@ int spring_reorder_fastq_N(spring_reorder_ctx *ctx, int32_t which, uint8_t *n_dn
                            uint32_t *order_N, uint32_t *count);
 
 /* ---- single-pool multi-GPU (one process per GPU).  Every rank loads the same
- * reads and builds the same dictionaries; rank r owns chains [r*K/world, (r+1)*K/world), K =
- * total_chains.  Per round: mg_search -> caller all-gathers the proposal words (mg_slice says which
- * bytes are this rank's) -> mg_apply.  Loop until *alive == 0, then mg_end + finalize/download as
- * usual (each rank then holds the streams of its own chains; tid of chain c is c % num_thr, so tid t
- * of the whole job is the concatenation over ranks of every rank's tid-t segment).  The result is
- * bit-identical to run_chains() with num_chains = total_chains on one GPU, whatever `world` is.
- * d_prop: device buffer of total_chains*8 bytes owned by the caller (e.g. a torch tensor it can hand
- * to torch.distributed), or NULL to let the library allocate it. */
+ * reads and builds the same dictionaries, then calls mg_begin with the same total_chains (K) and options.
+ * Chain ownership: with one chain group (stats.phases = 1) rank r owns the chains [r*K/world, (r+1)*K/world).
+ * With two groups (stats.phases = 2) the groups are cut from the global chain ids -- group 0 = [0, H), group 1 =
+ * [H, K), H = K/2 rounded to the nearest multiple of 2048 -- and rank r owns one slice of each: [r*H/world, (r+1)*H/world)
+ * and [H + r*(K-H)/world, H + (r+1)*(K-H)/world).
+ * Per round: mg_search -> the caller all-gathers the proposal words (8 bytes per chain, chain c at byte 8*c of the
+ * K*8-byte buffer) -> mg_apply.  mg_slices says where this rank's words are: *count slices (1 or 2), slice i at byte
+ * off[i] of length bytes[i]; the caller copies every rank's slices into every other rank's buffer at the same
+ * offsets, and that exchange must be COMPLETE (synchronised) on this rank's device before mg_apply is called: mg_apply
+ * reads every chain's word on the library's own stream.  mg_slice is the one-group form (E_STATE under two groups).
+ * Loop until *alive == 0 (every rank reports the same value), then mg_end + finalize/download as usual.
+ * Output: the tid of chain c is c % num_thr; each rank holds the streams of its own chains, chain ids ascending inside
+ * a tid.  The tid-t stream of the whole job -- chain ids ascending -- is, from spring_reorder_tid_split's mid[]:
+ * every rank's records [tid_off[t], mid[t]) (its group-0 slice), ranks ascending, then every rank's records
+ * [mid[t], tid_off[t+1]) (its group-1 slice), ranks ascending; likewise the singletons with mid_s.  With one group
+ * mid[t] = tid_off[t+1], i.e. the concatenation over ranks.  The result is bit-identical to run_chains() with
+ * num_chains = total_chains on one GPU, whatever `world` is.
+ * d_prop: device buffer of total_chains*8 bytes owned by the caller (e.g. a buffer it can hand to its own transport),
+ * or NULL to let the library allocate it (mg_slices / mg_slice return the pointer either way).  Who owns the buffer
+ * changes nothing: the schedule (one group or two) and the output are the same. */
 int spring_reorder_mg_begin(spring_reorder_ctx *ctx, uint32_t rank, uint32_t world, uint32_t total_chains, void *d_prop);
 int spring_reorder_mg_search(spring_reorder_ctx *ctx);
 int spring_reorder_mg_slice(spring_reorder_ctx *ctx, void **d_prop, size_t *slice_off, size_t *slice_bytes,
                             size_t *total_bytes);
+/* slice_off / slice_bytes: two entries each (entries past *count are 0); any pointer may be NULL. */
+int spring_reorder_mg_slices(spring_reorder_ctx *ctx, void **d_prop, size_t slice_off[2], size_t slice_bytes[2],
+                             size_t *total_bytes, uint32_t *count);
 int spring_reorder_mg_apply(spring_reorder_ctx *ctx, int32_t check_alive, uint32_t *alive);
 int spring_reorder_mg_end(spring_reorder_ctx *ctx);
-/* test hook, between mg_apply and the next mg_search: violations[0] = bitmap words with an untaken read above the cursor,
- * violations[1] = blocks below the cursor's block whose untaken-read count differs from the bitmap (what the seed pick,
- * reorder.h:576-592 on the GPU, relies on). */
-int spring_reorder_debug_check_seed_state(spring_reorder_ctx *ctx, uint64_t *violations);
+/* test hook, between mg_apply and the next mg_search, for chain group `group` (0, or 0 / 1 under two groups), in that
+ * group's view of the pool over its seed range ([0, n) with one group; with two, [nmid, n) for group 0 and [0, nmid)
+ * for group 1, nmid = n/2 rounded down to a multiple of 4096): violations[0] = bitmap words with an untaken read above
+ * the group's cursor, violations[1] = blocks below the cursor's block whose untaken-read count differs from the bitmap
+ * (what the seed pick, reorder.h:576-592 on the GPU, relies on). */
+int spring_reorder_debug_check_seed_state(spring_reorder_ctx *ctx, int32_t group, uint64_t *violations);
 /* all-gather between `world` contexts living in ONE process on one device (tests). */
 int spring_reorder_mg_exchange_virtual(spring_reorder_ctx **ctxs, uint32_t world);
 

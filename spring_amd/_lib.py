@@ -9,7 +9,8 @@ EXPORTS = [
     "spring_reorder_default_opts", "spring_reorder_last_error", "spring_reorder_trim_pool", "spring_reorder_run", "spring_reorder_create",
     "spring_reorder_destroy", "spring_reorder_load_dna", "spring_reorder_load_dna_device",
     "spring_reorder_build_dict", "spring_reorder_run_chains", "spring_reorder_auto_chains", "spring_reorder_finalize",
-    "spring_reorder_mg_begin", "spring_reorder_mg_search", "spring_reorder_mg_slice", "spring_reorder_mg_apply",
+    "spring_reorder_mg_begin", "spring_reorder_mg_search", "spring_reorder_mg_slice", "spring_reorder_mg_slices",
+    "spring_reorder_mg_apply",
     "spring_reorder_mg_end", "spring_reorder_mg_exchange_virtual", "spring_reorder_debug_check_seed_state",
     "spring_mg_rccl_unique_id", "spring_mg_comm_create_rccl", "spring_mg_comm_create_host", "spring_mg_comm_destroy",
     "spring_reorder_mg_run",
@@ -110,6 +111,9 @@ def lib():
     L.spring_reorder_mg_begin.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
     L.spring_reorder_mg_search.argtypes = [vp]
     L.spring_reorder_mg_slice.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.spring_reorder_mg_slices.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
+                                           C.POINTER(C.c_uint32)]
+    L.spring_reorder_debug_check_seed_state.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64)]
     L.spring_reorder_mg_apply.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint32)]
     L.spring_reorder_mg_end.argtypes = [vp]
     L.spring_reorder_mg_exchange_virtual.argtypes = [C.POINTER(vp), C.c_uint32]

@@ -1463,7 +1463,9 @@ static int setup_chains(spring_reorder_ctx *ctx, uint32_t K, uint32_t c0, uint32
     const uint32_t nmid = (uint32_t)(((uint64_t)n / 2) >> UBLK_SHIFT << UBLK_SHIFT);  // group 1's seeds: reads [0, nmid)
     // (n >= Ktot: every chain starts with a seed of its own, reorder.h:405-421 -- with fewer reads than chains only chain 0 runs, the
     // second group would have no chain at all and nobody would ever pick the seeds of its range)
-    const bool pool_ok = world == 1 ? (c0 == 0 && !d_prop)
+    // (world = 1: the whole pool, as run_chains runs it -- whoever owns the proposal buffer.  The words of both groups live in
+    // one buffer of Ktot words either way, and the output must not depend on who allocated it)
+    const bool pool_ok = world == 1 ? c0 == 0
                                     : ((uint64_t)K * world == Ktot && half % (MARK_BLOCK * world) == 0 && (Ktot - half) % (MARK_BLOCK * world) == 0);
     const bool can = allow_phases && fused && K > 0 && pool_ok && Ktot >= 4096 && half < Ktot && n < 0x80000000u && nmid > 0 && n >= Ktot;
     // Deep-bin pools (one chain per wavefront, up to 131 072 chains), one group / two, chains stage in ms: 20 M reads (131 072 chains)
@@ -1976,7 +1978,7 @@ int spring_reorder_run_chains(spring_reorder_ctx *ctx) {
 
 // ------------------------------------------------- single-pool multi-GPU
 // Every rank holds the full read pool and the dictionary table; rank r owns chains
-// [r*K/world, (r+1)*K/world).  One round = mg_search (k_round over the own chains: apply of the last
+// [r*K/world, (r+1)*K/world), or under two chain groups one slice of each (ctx->grp).  One round = mg_search (k_round over the own chains: apply of the last
 // proposals + search) -> all-gather of the per-chain proposal words (mg_run: inside the library; the
 // step-wise API: by the caller, or spring_reorder_mg_exchange_virtual between contexts of one process) ->
 // mg_apply (k_mg_resolve + k_mg_mark over all chains, on every rank identically).
@@ -2020,11 +2022,27 @@ int spring_reorder_mg_search(spring_reorder_ctx *ctx) {
 int spring_reorder_mg_slice(spring_reorder_ctx *ctx, void **d_prop, size_t *slice_off, size_t *slice_bytes,
                             size_t *total_bytes) {
   if (!ctx || !ctx->mg) return fail(SPRING_REORDER_E_STATE, "mg_slice: mg_begin first");
-  if (ctx->P.phases == 2) return fail(SPRING_REORDER_E_STATE, "mg_slice: with two chain groups a rank owns two slices of the proposal words (mg_run / exchange_virtual move both)");
+  if (ctx->P.phases == 2) return fail(SPRING_REORDER_E_STATE, "mg_slice: with two chain groups a rank owns two slices of the proposal words: ask mg_slices");
   if (d_prop) *d_prop = ctx->P.prop;
   if (slice_off) *slice_off = (size_t)ctx->P.c0 * 8;
   if (slice_bytes) *slice_bytes = (size_t)ctx->P.K * 8;
   if (total_bytes) *total_bytes = (size_t)ctx->P.Ktot * 8;
+  return 0;
+}
+
+// this rank's slices of the proposal words: one, or one per chain group (the geometry exchange_virtual and mg_run_phased move)
+int spring_reorder_mg_slices(spring_reorder_ctx *ctx, void **d_prop, size_t *slice_off, size_t *slice_bytes,
+                             size_t *total_bytes, uint32_t *count) {
+  if (!ctx || !ctx->mg) return fail(SPRING_REORDER_E_STATE, "mg_slices: mg_begin first");
+  const uint32_t ns = ctx->P.phases == 2 ? 2u : 1u;
+  if (d_prop) *d_prop = ctx->P.prop;
+  for (uint32_t g = 0; g < 2; g++) {
+    const auto &a = ctx->grp[g];
+    if (slice_off) slice_off[g] = g < ns ? ((size_t)a.c0 + a.g0) * 8 : 0;  // (c0 + g0: the slice's first global chain id)
+    if (slice_bytes) slice_bytes[g] = g < ns ? (size_t)a.Kg * 8 : 0;
+  }
+  if (total_bytes) *total_bytes = (size_t)ctx->P.Ktot * 8;
+  if (count) *count = ns;
   return 0;
 }
 
@@ -2067,15 +2085,29 @@ int spring_reorder_mg_end(spring_reorder_ctx *ctx) {
   return 0;
 }
 
-// test hook: the invariants the seed pick relies on, checked between two rounds of the step-wise API (after mg_apply)
-int spring_reorder_debug_check_seed_state(spring_reorder_ctx *ctx, uint64_t *violations /* [2] */) {
+// test hook: the invariants the seed pick of chain group `group` relies on, checked between two rounds of the step-wise API
+// (after mg_apply, before the next mg_search).  A group's find_seed reads its own view (taken / taken2), its own cursor and
+// ublk[] over its own seed range [seed_lo, seed_hi) -- [0, n) with one group; with two, [nmid, n) for group 0 and [0, nmid)
+// for group 1 (nmid is a whole number of blocks, so every block of ublk[] belongs to one group).  Every write those reads
+// depend on is made by the group's own mark step (k_ph_mark[_wide]): its winners, and the other group's winners of the mark
+// step in front of it (won_other), folded into its view AND out of ublk[] of its range in the same launch.  So the view
+// and the counts of a group agree at the end of each of its mark steps; mg_apply runs both (A, then B), and the check
+// holds from there to the next mg_search.  (Between A and B group 1's view still lacks group 0's winners of the round, and
+// so does ublk[] of its range -- they agree there too, but no caller can stop in between.)
+int spring_reorder_debug_check_seed_state(spring_reorder_ctx *ctx, int32_t group, uint64_t *violations /* [2] */) {
   if (!ctx || !ctx->mg || ctx->stage != ST_DICT || !violations) return fail(SPRING_REORDER_E_STATE, "debug_check_seed_state: between mg_begin and mg_end");
+  const int ng = ctx->P.phases == 2 ? 2 : 1;
+  if (group < 0 || group >= ng) return fail(SPRING_REORDER_E_ARG, "debug_check_seed_state: group %d, the chains run as %d group(s)", group, ng);
   HIPCHK(hipSetDevice(ctx->dev));
+  const DevParams Q = ng == 2 ? group_params(ctx, group, ctx->round_no) : ctx->P;
   unsigned long long *d_bad = nullptr;
   DMALLOC(d_bad, 16);
   HIPCHK(hipMemsetAsync(d_bad, 0, 16, ctx->st));
-  const uint64_t nblk = ((uint64_t)ctx->n + (1ull << UBLK_SHIFT) - 1) >> UBLK_SHIFT;
-  launch_check_seed_state(ctx->st, ctx->P, nblk << (UBLK_SHIFT - 6), d_bad);
+  const uint64_t nwords = (((uint64_t)ctx->n + (1ull << UBLK_SHIFT) - 1) >> UBLK_SHIFT) << (UBLK_SHIFT - 6);
+  // (the range whose reads above the cursor must be taken: up to seed_hi, or -- the range that ends at n -- through the
+  // padding of the last block, whose bits find_seed reads as taken)
+  const uint64_t hi = Q.seed_hi >= ctx->n ? nwords * 64 : Q.seed_hi;
+  launch_check_seed_state(ctx->st, Q, nwords, hi, d_bad);
   unsigned long long h[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(h, d_bad, 16, hipMemcpyDeviceToHost, ctx->st));
   HIPCHK(hipStreamSynchronize(ctx->st));

@@ -59,17 +59,24 @@ class _MgStage(ReorderStage):
     def mg_end(self):
         _chk(self._L.spring_reorder_mg_end(self._h))
 
-    def check_seed_state(self):
-        """Between two rounds: (bitmap words with an untaken read above the cursor, blocks below the cursor's block
-        whose untaken-read count is off) -- both must be zero for the seed pick to be exact."""
+    def check_seed_state(self, group=0):
+        """Between two rounds, for chain group `group`: (bitmap words of the group's view with an untaken read of its seed
+        range above its cursor, blocks of that range below the cursor's block whose untaken-read count is off) -- both must
+        be zero for the group's seed pick to be exact."""
         v = (C.c_uint64 * 2)()
-        _chk(self._L.spring_reorder_debug_check_seed_state(self._h, v))
+        _chk(self._L.spring_reorder_debug_check_seed_state(self._h, int(group), v))
         return int(v[0]), int(v[1])
 
     def mg_slice(self):
         p, off, nb, tot = C.c_void_p(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         _chk(self._L.spring_reorder_mg_slice(self._h, C.byref(p), C.byref(off), C.byref(nb), C.byref(tot)))
         return p.value, off.value, nb.value, tot.value
+
+    def mg_slices(self):
+        """-> (proposal buffer, [(byte offset, bytes)] of this rank's slices -- one per chain group --, total bytes)."""
+        p, off, nb, tot, cnt = C.c_void_p(), (C.c_size_t * 2)(), (C.c_size_t * 2)(), C.c_size_t(), C.c_uint32()
+        _chk(self._L.spring_reorder_mg_slices(self._h, C.byref(p), off, nb, C.byref(tot), C.byref(cnt)))
+        return p.value, [(int(off[i]), int(nb[i])) for i in range(cnt.value)], tot.value
 
 
 class VirtualPool:
@@ -88,8 +95,7 @@ class VirtualPool:
         for r, s in enumerate(self.stages):
             s.mg_begin(r, self.world, self.K)
         arr = (C.c_void_p * self.world)(*[s._h for s in self.stages])
-        # (two chain groups: every group has its own view of the pool and its own seed range; the debug check below knows one)
-        one_group = int(self.stages[0].stats()["phases"]) != 2
+        groups = int(self.stages[0].stats()["phases"])  # (two chain groups: each has its own view of the pool and seed range)
         rounds = 0
         while True:
             for s in self.stages:
@@ -97,9 +103,10 @@ class VirtualPool:
             _chk(L_.spring_reorder_mg_exchange_virtual(arr, self.world))
             alive = [s.mg_apply(True) for s in self.stages]
             rounds += 1
-            if one_group and rounds % self.check_every == 0:  # what find_seed relies on, on every rank's replica
-                for s in self.stages:
-                    assert s.check_seed_state() == (0, 0), "seed-pick invariants broken after round %d" % rounds
+            if rounds % self.check_every == 0:  # what find_seed relies on, on every rank's replica of every group's view
+                for r, s in enumerate(self.stages):
+                    for g in range(groups):
+                        assert s.check_seed_state(g) == (0, 0), "seed-pick invariants of group %d broken on rank %d after round %d" % (g, r, rounds)
             assert len(set(alive)) == 1, "ranks disagree on the number of running chains: %r" % (alive,)
             if alive[0] == 0:
                 break
