@@ -6,13 +6,16 @@ batch of synthetic reads that is already resident in HBM as a .dna record stream
 region starts.  N=1 workload = BASELINE configs[2]: 100 M x 150 bp single-end.  For every N>1 the job is the SAME
 shared read pool -- BASELINE configs[4], 400 M x 150 bp, which also fits one GPU (108 GB) -- with the chains sharded
 over the GPUs and one RCCL all-gather of the proposal words per round, issued by the library on its own stream
-(spring_reorder_mg_run): total work is fixed, `"scaling": "strong"`, `value` = pool reads / wall-clock, and rank 0
-also runs that pool alone so the line carries the single-GPU rate it is to be compared with; see DESIGN.md
+(spring_reorder_mg_run): total work is fixed, `"scaling": "strong"`, `value` = pool reads / wall-clock, and under
+--full rank 0 also runs that pool alone so the line carries the single-GPU rate it is to be compared with; see DESIGN.md
 "Multi-GPU".  --lanes switches the N>1 run to independent lanes (one read set per GPU, no data-path collective).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the
-round kernel, `cpu_baseline` (the C oracle timed on a bounded sample of the same workload) and `compression_cost`
-(what the default chain count costs in compressed size, real BSC).  --dump-outputs DIR writes what the last timed step
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the steps and
+prints that line, nothing more.  --full adds every leg that runs beside the headline: `roofline` for the round kernel,
+`encoder_stage`, `stage_incl_pcie` / `stage_incl_files`, `coverage_sweep`, `cpu_baseline` (the C oracle timed on a
+bounded sample of the same workload) and `compression_cost` (what the default chain count costs in compressed size,
+real BSC); for the shared pool, `round_budget` and `single_gpu_same_pool`.  The options that size or skip those legs
+(--cpu-sample, --no-roofline, --no-single, ...) act under --full.  --dump-outputs DIR writes what the last timed step
 computed (its output streams, sampled to at most 64 MB) for output-for-output comparison of two builds; that step's
 stage is freed after the timer stops instead of inside the step.
 """
@@ -44,6 +47,9 @@ def parse():
     ap.add_argument("--err-ppm", type=int, default=10000)
     ap.add_argument("--chains", type=int, default=0, help="0 = library default")
     ap.add_argument("--num-thr", type=int, default=8, help="per-tid output sets (reference default -t 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run the legs beside it (roofline, encoder stage, PCIe and file spans, coverage "
+                         "sweep, CPU baseline, compression cost; for the shared pool the round budget and rank 0's single-GPU pass)")
     ap.add_argument("--cpu-sample", type=int, default=100_000_000,
                     help="reads in the CPU-baseline sample (0 = skip); the default is the whole workload (~105 s at 32 threads)")
     ap.add_argument("--cpu-files-sample", type=int, default=16_000_000, help="reads in the CPU twin of stage_incl_files")
@@ -353,56 +359,57 @@ def _pool_run(a, lanes, torch, spring_amd, L_):
     el, st = lanes.timed_steps(one_pass, a.steps, a.warmup)
     tot_matched = lanes.sum_over_ranks(st["local_matched"])
     tot_single = lanes.sum_over_ranks(st["local_single"])
-    # one more pass with HIP events around the three pieces of a round (outside the timed region): where a round goes
-    stt = one_pass(time_search=True)
-    rounds = max(stt["search_launches"], 1)
-    groups = max(int(stt.get("phases", 1)), 1)
-    budget = {"rounds": stt["rounds"], "chain_groups": groups,
-              "round_kernel_us": round(stt["ms_search_kernel"] * 1e3 / rounds, 1),
-              "exchange_us": round(stt["ms_exchange"] * 1e3 / rounds, 1),
-              "resolve_and_mark_us": round(stt["ms_resolve_mark"] * 1e3 / rounds, 1),
-              "replicated_ms": {"unpack": round(stt["ms_unpack"], 1), "dictionaries": round(stt["ms_dict"], 1),
-                                "finalize": round(stt["ms_finalize"], 1)},
-              "chains_ms": round(stt["ms_chains"], 1),
-              "what": "rank 0, per round: k_round over the rank's own chains | all-gather of the proposal words | "
-                      "k_mg_resolve + k_mg_mark over ALL chains (replicated work, grows with N); replicated_ms is work every "
-                      "rank repeats for the whole pool"}
-    if groups == 2:
-        # two chain groups: a rank owns a slice of each; a group's all-gather (on the exchange stream), resolve and mark run
-        # beside the OTHER group's round kernel.  round_kernels_busy_ms = the time during which at least one round kernel of
-        # the rank ran (union of the launches' intervals); chains_ms beyond it is what the exchange + resolve + mark still
-        # cost the critical path.  resolve_and_mark_us includes the mark step's wait for the other group's mark step.
-        busy = stt.get("ms_search_busy") or 0.0
-        budget.update({
-            "per": "group-round (a round of one chain group: half of the rank's chains)",
-            "round_kernels_busy_ms": round(busy, 1),
-            "off_the_round_kernels_ms": round(max(stt["ms_chains"] - busy, 0.0), 1),
-            "off_the_round_kernels_frac": round(max(stt["ms_chains"] - busy, 0.0) / max(stt["ms_chains"], 1e-9), 4),
-            "what": "rank 0, per group-round: k_round over the rank's slice of the group | in-place all-gather of the group's proposal "
-                    "words on the exchange stream | k_mg_resolve + the group's mark step over the whole group (replicated), which "
-                    "also waits for the other group's mark step; these run beside the other group's round kernel: chains_ms - "
-                    "round_kernels_busy_ms is what they leave on the critical path (timed pass: a batch of rounds at a time)"})
-    # the single-GPU rate on the SAME pool and chain count (rank 0 alone, the others wait): what `value` is to be divided by
-    single = None
-    if world > 1 and not a.no_single:
-        lanes.barrier()
-        if rank == 0:
-            try:
-                t0 = time.perf_counter()
-                s1 = spring_amd.ReorderStage(spring_amd.ReorderOpts(device=dev, num_chains=Ktot, num_thr=a.num_thr))
-                s1.load_dna_device(buf.data_ptr(), nb, n, L, True)
-                s1.run()
-                s1s = s1.stats()
-                s1.close()
-                t1 = time.perf_counter() - t0
-                single = {"value": round(n / t1 / 1e6, 3), "unit": "Mreads/s", "seconds": round(t1, 3), "rounds": s1s["rounds"],
-                          "chain_groups": int(s1s.get("phases", 1)),
-                          "what": "the same pool and chain count on rank 0's GPU alone (one pass incl. allocations), with the "
-                                  "library's choice of the schedule (two chain groups whose rounds alternate, in the pool as well: "
-                                  "the same output)"}
-            except Exception as e:  # noqa: BLE001
-                single = {"error": repr(e)}
-        lanes.barrier()
+    budget = single = None
+    if a.full:
+        # one more pass with HIP events around the three pieces of a round (outside the timed region): where a round goes
+        stt = one_pass(time_search=True)
+        rounds = max(stt["search_launches"], 1)
+        groups = max(int(stt.get("phases", 1)), 1)
+        budget = {"rounds": stt["rounds"], "chain_groups": groups,
+                  "round_kernel_us": round(stt["ms_search_kernel"] * 1e3 / rounds, 1),
+                  "exchange_us": round(stt["ms_exchange"] * 1e3 / rounds, 1),
+                  "resolve_and_mark_us": round(stt["ms_resolve_mark"] * 1e3 / rounds, 1),
+                  "replicated_ms": {"unpack": round(stt["ms_unpack"], 1), "dictionaries": round(stt["ms_dict"], 1),
+                                    "finalize": round(stt["ms_finalize"], 1)},
+                  "chains_ms": round(stt["ms_chains"], 1),
+                  "what": "rank 0, per round: k_round over the rank's own chains | all-gather of the proposal words | "
+                          "k_mg_resolve + k_mg_mark over ALL chains (replicated work, grows with N); replicated_ms is work every "
+                          "rank repeats for the whole pool"}
+        if groups == 2:
+            # two chain groups: a rank owns a slice of each; a group's all-gather (on the exchange stream), resolve and mark run
+            # beside the OTHER group's round kernel.  round_kernels_busy_ms = the time during which at least one round kernel of
+            # the rank ran (union of the launches' intervals); chains_ms beyond it is what the exchange + resolve + mark still
+            # cost the critical path.  resolve_and_mark_us includes the mark step's wait for the other group's mark step.
+            busy = stt.get("ms_search_busy") or 0.0
+            budget.update({
+                "per": "group-round (a round of one chain group: half of the rank's chains)",
+                "round_kernels_busy_ms": round(busy, 1),
+                "off_the_round_kernels_ms": round(max(stt["ms_chains"] - busy, 0.0), 1),
+                "off_the_round_kernels_frac": round(max(stt["ms_chains"] - busy, 0.0) / max(stt["ms_chains"], 1e-9), 4),
+                "what": "rank 0, per group-round: k_round over the rank's slice of the group | in-place all-gather of the group's proposal "
+                        "words on the exchange stream | k_mg_resolve + the group's mark step over the whole group (replicated), which "
+                        "also waits for the other group's mark step; these run beside the other group's round kernel: chains_ms - "
+                        "round_kernels_busy_ms is what they leave on the critical path (timed pass: a batch of rounds at a time)"})
+        # the single-GPU rate on the SAME pool and chain count (rank 0 alone, the others wait): what `value` is to be divided by
+        if world > 1 and not a.no_single:
+            lanes.barrier()
+            if rank == 0:
+                try:
+                    t0 = time.perf_counter()
+                    s1 = spring_amd.ReorderStage(spring_amd.ReorderOpts(device=dev, num_chains=Ktot, num_thr=a.num_thr))
+                    s1.load_dna_device(buf.data_ptr(), nb, n, L, True)
+                    s1.run()
+                    s1s = s1.stats()
+                    s1.close()
+                    t1 = time.perf_counter() - t0
+                    single = {"value": round(n / t1 / 1e6, 3), "unit": "Mreads/s", "seconds": round(t1, 3), "rounds": s1s["rounds"],
+                              "chain_groups": int(s1s.get("phases", 1)),
+                              "what": "the same pool and chain count on rank 0's GPU alone (one pass incl. allocations), with the "
+                                      "library's choice of the schedule (two chain groups whose rounds alternate, in the pool as well: "
+                                      "the same output)"}
+                except Exception as e:  # noqa: BLE001
+                    single = {"error": repr(e)}
+            lanes.barrier()
     out = {
         "metric": "Mreads/s through reorder stage", "value": round(n * a.steps / el / 1e6, 3), "unit": "Mreads/s",
         "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(el / a.steps * 1e3, 3),
@@ -419,11 +426,11 @@ def _pool_run(a, lanes, torch, spring_amd, L_):
             "stage_ms_rank0": {k: round(st[k], 2) for k in ("ms_unpack", "ms_dict", "ms_chains", "ms_finalize")},
             "rounds": st["rounds"], "reads_emitted_all_ranks": int(tot_matched + tot_single),
             "note": "strong scaling: pool and chain count are the same for every N > 1; at N=1 the bench runs BASELINE "
-                    "configs[2] (100 M reads) instead, so compare with single_gpu_same_pool, not with the N=1 line",
+                    "configs[2] (100 M reads) instead, so compare with single_gpu_same_pool (--full), not with the N=1 line",
         },
-        "round_budget": budget,
-        "single_gpu_same_pool": single,
     }
+    if a.full:
+        out.update({"round_budget": budget, "single_gpu_same_pool": single})
     if rank == 0:
         assert int(tot_matched + tot_single) == n, "the ranks' streams do not add up to the pool"
     comm.close()
@@ -484,8 +491,10 @@ def main():
         print("# --dump-outputs %s: %s" % (a.dump_outputs, ", ".join("%s %d of %d" % (k, m, sz) for k, (sz, m) in written.items())),
               file=sys.stderr, flush=True)
     out = headline_line(a, world, el, st, G)
+    # --full: the legs beside the headline (rank 0 of a single-GPU run); a plain run goes straight to the line
+    full = a.full and rank == 0 and world == 1
 
-    if rank == 0 and world == 1 and not a.no_roofline:
+    if full and not a.no_roofline:
         # three extra passes: (1) the production round kernel (k_round = apply of the last proposals + search, 85 % of
         # the GPU time) with a HIP-event pair around every launch, on the library's stream; (2) the counting variant
         # for the reference-equivalent work counters (slower, so it is not the one that is timed); (3) the two-kernel
@@ -569,7 +578,7 @@ def main():
                 "avg_launch_us": round(ms2 * 1e3 / l2, 2), "achieved": round(a2, 2), "frac": round(a2 / HBM_PEAK_GBS, 5),
                 "algorithmic_bytes_per_launch": round(alg_search / l2, 1),
                 "stage_ms_chains_two_kernel_round": round(st_2k["ms_chains"], 2)}
-    if rank == 0 and world == 1 and not a.no_roofline:
+    if full and not a.no_roofline:
         # row f2: the encoder stage chained on the same workload, streams never leave HBM.
         # Reported beside the headline, never part of `value`.
         try:
@@ -591,7 +600,7 @@ def main():
             }
         except Exception as e:  # the widened row must never break the headline line
             out["encoder_stage"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not a.no_roofline:
+    if full and not a.no_roofline:
         # SURVEY 8(d) legs (ii) and (iii), reported beside `value` (never part of it):
         # (ii) stage incl. PCIe: the .dna record stream starts in HOST memory and every output stream ends there
         try:
@@ -643,7 +652,7 @@ def main():
                                                    "the %d per-tid file sets + singleton files (%.2f GB)" % (recb / 1e9, a.num_thr, out_bytes / 1e9)}
             except Exception as e:
                 out["stage_incl_files"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not a.no_roofline and a.sweep_sample > 0:
+    if full and not a.no_roofline and a.sweep_sample > 0:
         # Beside the headline, never part of `value`: the stage on pools of other depths with the library's defaults
         # (chain count, kernel variant, probe plan, k_long all chosen from the dictionary) -- every BASELINE config is
         # uniform 25x, real read sets are not.  Second, warm run of each pool.
@@ -681,7 +690,7 @@ def main():
                                      "what": "the same stage, library defaults, inputs resident in HBM, whole-stage wall clock"}
         except Exception as e:  # noqa: BLE001
             out["coverage_sweep"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and a.cpu_sample > 0:
+    if full and a.cpu_sample > 0:
         # CPU baseline on the GPU box's host cores: the C port of the reference algorithm
         # (oracle/reorder_oracle.c).  Multi-thread leg = free-running OpenMP chains like the
         # reference's `-t T` (orc_reorder_omp); single-thread leg = the `-t 1` restatement.
@@ -744,7 +753,7 @@ def main():
             del readg, lng, dnag
         except Exception as e:  # noqa: BLE001
             out["cpu_baseline"]["genome_like"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and a.cpu_sample > 0 and "cpu_baseline" in out:
+    if full and a.cpu_sample > 0 and "cpu_baseline" in out:
         # the reference's own span ("Time for this step", spring.cpp:152-160): input_clean_1.dna from disk, load,
         # dictionaries, reorder, and the per-tid output files written -- the CPU twin of stage_incl_files
         try:
@@ -782,7 +791,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["cpu_baseline"]["stage_incl_files_value"] = None
             out["cpu_baseline"]["stage_incl_files_error"] = repr(e)
-    if rank == 0 and world == 1 and a.cost_sample > 0 and not a.no_roofline:
+    if full and a.cost_sample > 0 and not a.no_roofline:
         # what the speed costs: compressed size of the encoder's output streams after the REFERENCE'S OWN BSC (src/libbsc
         # compiled in place, test infrastructure oracle/_ref/ref_bsc, outside any timed region) for the default chain
         # count against the reference's own granularity K = num_thr, same reads
