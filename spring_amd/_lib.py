@@ -24,6 +24,13 @@ EXPORTS = [
     "spring_encoder_download_seq_packed", "spring_encoder_get_info", "spring_reorder_encode_run", "spring_encoder_encode_host", "spring_encoder_run",
 ]
 
+# include/spring_streams.h: a list of its own (EXPORTS mirrors spring_reorder.h + spring_encoder.h exactly)
+STREAMS_EXPORTS = [
+    "spring_streams_create", "spring_streams_destroy", "spring_streams_from_encoder", "spring_streams_from_host",
+    "spring_streams_download", "spring_streams_get_info", "spring_streams_run",
+]
+STREAMS_NUM = 9  # SPRING_STREAMS_NUM
+
 
 class Opts(C.Structure):
     _fields_ = [("device", C.c_int32), ("num_chains", C.c_uint32), ("num_thr", C.c_int32),
@@ -48,6 +55,19 @@ class EncoderInfo(C.Structure):
                                            "unaligned_bytes", "len_unaligned", "num_contigs")]
                 + [(k, C.c_uint32) for k in ("matched_s", "matched_N", "align_passes", "max_bin")]
                 + [("ms_device", C.c_double), ("ms_phase", C.c_double * 8)])
+
+    def asdict(self):
+        d = {}
+        for k, _ in self._fields_:
+            v = getattr(self, k)
+            d[k] = list(v) if hasattr(v, "__len__") else v
+        return d
+
+
+class StreamsInfo(C.Structure):
+    _fields_ = ([("num_units", C.c_uint64), ("num_blocks", C.c_uint64), ("bytes", C.c_uint64 * STREAMS_NUM),
+                 ("flag_count", C.c_uint64 * 5), ("pos_escapes", C.c_uint64), ("n_aligned", C.c_uint64),
+                 ("ms_device", C.c_double), ("ms_file", C.c_double)])
 
     def asdict(self):
         d = {}
@@ -158,6 +178,20 @@ def lib():
     L.spring_encoder_get_info.argtypes = [vp, C.POINTER(EncoderInfo)]
     L.spring_reorder_encode_run.argtypes = [C.c_char_p, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                             C.c_uint32, C.POINTER(Opts), C.POINTER(EncoderInfo)]
+    L.spring_streams_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.spring_streams_destroy.argtypes = [vp]
+    L.spring_streams_destroy.restype = None
+    L.spring_streams_from_encoder.argtypes = [vp, vp, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32,
+                                              C.POINTER(StreamsInfo)]
+    L.spring_streams_from_host.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp,
+                                           C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(StreamsInfo)]
+    L.spring_streams_download.argtypes = [vp, C.c_int32, vp, vp]
+    L.spring_streams_get_info.argtypes = [vp, C.POINTER(StreamsInfo)]
+    L.spring_streams_run.argtypes = [C.c_char_p, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32,
+                                     C.POINTER(StreamsInfo)]
+    for name in STREAMS_EXPORTS:
+        if name != "spring_streams_destroy":
+            getattr(L, name).restype = C.c_int
     for name in EXPORTS:
         if name not in ("spring_reorder_last_error", "spring_reorder_destroy", "spring_synth_dna_bytes",
                         "spring_reorder_default_opts", "spring_reorder_trim_pool", "spring_encoder_destroy",

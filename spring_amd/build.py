@@ -9,16 +9,17 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libspring_reorder_hip.so")
 SOURCES = ["reorder_kernels.hip", "reorder_pipeline.cpp", "reorder_files.cpp", "order_ops.hip", "fastq_kernels.hip",
-           "encoder.hip", "fastq_reorder.hip"]
-HEADERS = ["reorder_device.h", "reorder_internal.h", "reorder_round_mc.h", "synth_common.h", "call_reorder.h"]
+           "encoder.hip", "fastq_reorder.hip", "streams.hip"]
+HEADERS = ["reorder_device.h", "reorder_internal.h", "reorder_round_mc.h", "synth_common.h", "call_reorder.h",
+           "encoder_internal.h"]
+PUBLIC_HEADERS = ["spring_reorder.h", "spring_encoder.h", "spring_streams.h"]
 
 
 def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(ROOT, "include", "spring_reorder.h"),
-                                                            os.path.join(ROOT, "include", "spring_encoder.h")]
+    deps = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(ROOT, "include", h) for h in PUBLIC_HEADERS]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -33,7 +34,7 @@ def build(force=False, verbose=False):
         objs.append(obj)
         if not force and os.path.exists(obj) and os.path.getmtime(obj) > max(
                 os.path.getmtime(os.path.join(CSRC, f)) for f in [src] + HEADERS) and os.path.getmtime(obj) > max(
-                os.path.getmtime(os.path.join(ROOT, "include", h)) for h in ("spring_reorder.h", "spring_encoder.h")):
+                os.path.getmtime(os.path.join(ROOT, "include", h)) for h in PUBLIC_HEADERS):
             continue  # object newer than its source and every header
         cmds.append([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-x", "hip",
                      "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-c", os.path.join(CSRC, src), "-o", obj])

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
+#include "encoder_internal.h"
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_encoder.h"
@@ -1427,3 +1428,20 @@ int spring_encoder_download_seq_packed(spring_encoder_ctx *ctx, uint8_t *packed,
 }
 
 }  // extern "C"
+
+namespace sr {
+int encoder_view(spring_encoder_ctx *ctx, EncoderView *v) {
+  if (!ctx || !v) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  if (!ctx->have) return fail(SPRING_REORDER_E_STATE, "nothing encoded yet");
+  v->dev = ctx->dev;
+  v->info = ctx->info;
+  v->pos = ctx->pos.as<uint64_t>();
+  v->noise = ctx->noise.as<char>();
+  v->noisepos = ctx->noisepos.as<uint16_t>();
+  v->order = ctx->order.as<uint32_t>();
+  v->rlen = ctx->rlen.as<uint16_t>();
+  v->rc = ctx->rc.as<char>();
+  v->unaligned = ctx->unaligned.as<uint8_t>();
+  return 0;
+}
+}  // namespace sr

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
+#include "encoder_internal.h"
 #include "reorder_device.h"
 #include "spring_reorder.h"
 
@@ -156,6 +157,32 @@ int spring_order_correct(uint32_t *order, uint64_t m, const uint32_t *order_N, u
   if (kernel_ms) *kernel_ms = ms;
   return 0;
 }
+
+}  // extern "C"
+
+namespace sr {
+// the kernels of spring_order_pe_encode on device arrays, queued on st (the streams stage applies pe_encode to a
+// private copy of the encoder's order without a host round trip)
+int pe_encode_device(hipStream_t st, const uint32_t *order, uint32_t n, uint32_t *out) {
+  if (n & 1) return fail(SPRING_REORDER_E_ARG, "pe_encode needs an even number of reads (pairs)");
+  if (!n) return 0;
+  const uint32_t half = n / 2;
+  Buf dinv, dflag, drank, dtmp;
+  HIPCHK(dinv.alloc((size_t)n * 4)); HIPCHK(dflag.alloc((size_t)n * 4)); HIPCHK(drank.alloc((size_t)n * 4));
+  size_t tb = 0;
+  HIPCHK(sr::excl_scan_u32(st, nullptr, tb, dflag.as<uint32_t>(), drank.as<uint32_t>(), n));
+  HIPCHK(dtmp.alloc(tb));
+  hipLaunchKernelGGL(k_invert_se, grid(n), dim3(256), 0, st, order, n, dinv.as<uint32_t>());
+  hipLaunchKernelGGL(k_flag_lt, grid(n), dim3(256), 0, st, order, n, half, dflag.as<uint32_t>());
+  HIPCHK(sr::excl_scan_u32(st, dtmp.p, tb, dflag.as<uint32_t>(), drank.as<uint32_t>(), n));
+  hipLaunchKernelGGL(k_pe_encode, grid(n), dim3(256), 0, st, order, dinv.as<uint32_t>(), drank.as<uint32_t>(), n, half,
+                     out);
+  HIPCHK(hipStreamSynchronize(st));  // the scratch buffers are freed on return
+  return 0;
+}
+}  // namespace sr
+
+extern "C" {
 
 int spring_order_pe_encode(const uint32_t *order, uint32_t n, uint32_t *new_order, double *kernel_ms) {
   if (n && (!order || !new_order)) return fail(SPRING_REORDER_E_ARG, "NULL argument");
