@@ -6,3 +6,4 @@ anywhere, running requires the built library and a GPU."""
 from .reorder import (CompressionParams, ReorderError, ReorderOpts, ReorderStage, call_reorder, reorder_dna,  # noqa: F401
                       synth_dna_host, synth_genome_host, SYNTH_GENOMIC, SYNTH_PAIRED, SYNTH_REPEATS)
 from .streams import StreamsStage, call_reorder_compress_streams  # noqa: F401,E402
+from .decode import DecodeStage  # noqa: F401,E402

@@ -31,6 +31,13 @@ STREAMS_EXPORTS = [
 ]
 STREAMS_NUM = 9  # SPRING_STREAMS_NUM
 
+# include/spring_decode.h: a list of its own as well
+DECODE_EXPORTS = [
+    "spring_decode_create", "spring_decode_destroy", "spring_decode_seq_from_encoder", "spring_decode_seq_from_host",
+    "spring_decode_seq_from_files", "spring_decode_from_streams", "spring_decode_from_host", "spring_decode_from_files",
+    "spring_decode_download", "spring_decode_get_info",
+]
+
 
 class Opts(C.Structure):
     _fields_ = [("device", C.c_int32), ("num_chains", C.c_uint32), ("num_thr", C.c_int32),
@@ -68,6 +75,20 @@ class StreamsInfo(C.Structure):
     _fields_ = ([("num_units", C.c_uint64), ("num_blocks", C.c_uint64), ("bytes", C.c_uint64 * STREAMS_NUM),
                  ("flag_count", C.c_uint64 * 5), ("pos_escapes", C.c_uint64), ("n_aligned", C.c_uint64),
                  ("ms_device", C.c_double), ("ms_file", C.c_double)])
+
+    def asdict(self):
+        d = {}
+        for k, _ in self._fields_:
+            v = getattr(self, k)
+            d[k] = list(v) if hasattr(v, "__len__") else v
+        return d
+
+
+class DecodeInfo(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("seq_len", "first_block", "num_blocks", "num_units")]
+                + [("bases", C.c_uint64 * 2)]
+                + [(k, C.c_uint64) for k in ("n_aligned", "n_unaligned", "pos_escapes")]
+                + [("ms_device", C.c_double), ("ms_file", C.c_double)])
 
     def asdict(self):
         d = {}
@@ -189,6 +210,22 @@ def lib():
     L.spring_streams_get_info.argtypes = [vp, C.POINTER(StreamsInfo)]
     L.spring_streams_run.argtypes = [C.c_char_p, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32,
                                      C.POINTER(StreamsInfo)]
+    L.spring_decode_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.spring_decode_destroy.argtypes = [vp]
+    L.spring_decode_destroy.restype = None
+    L.spring_decode_seq_from_encoder.argtypes = [vp, vp]
+    L.spring_decode_seq_from_host.argtypes = [vp, C.c_int32, vp, vp, vp]
+    L.spring_decode_seq_from_files.argtypes = [vp, C.c_char_p, C.c_int32]
+    L.spring_decode_from_streams.argtypes = [vp, vp, C.POINTER(DecodeInfo)]
+    L.spring_decode_from_host.argtypes = [vp, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
+                                          C.c_uint32, C.POINTER(DecodeInfo)]
+    L.spring_decode_from_files.argtypes = [vp, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
+                                           C.c_uint32, C.POINTER(DecodeInfo)]
+    L.spring_decode_download.argtypes = [vp, C.c_int32, vp, vp]
+    L.spring_decode_get_info.argtypes = [vp, C.POINTER(DecodeInfo)]
+    for name in DECODE_EXPORTS:
+        if name != "spring_decode_destroy":
+            getattr(L, name).restype = C.c_int
     for name in STREAMS_EXPORTS:
         if name != "spring_streams_destroy":
             getattr(L, name).restype = C.c_int

@@ -1442,6 +1442,9 @@ int encoder_view(spring_encoder_ctx *ctx, EncoderView *v) {
   v->rlen = ctx->rlen.as<uint16_t>();
   v->rc = ctx->rc.as<char>();
   v->unaligned = ctx->unaligned.as<uint8_t>();
+  v->refc = ctx->refc.as<uint8_t>();
+  v->num_thr = ctx->T;
+  v->tid_seq = ctx->tid_seq.data();
   return 0;
 }
 }  // namespace sr

@@ -20,6 +20,9 @@ struct EncoderView {
   const uint16_t *rlen;       // read_lengths.bin
   const char *rc;             // read_rev.txt
   const uint8_t *unaligned;   // read_unaligned.txt (write_dnaN_in_bits records)
+  const uint8_t *refc;        // the consensus, one byte per base, SPRING code A0 G1 C2 T3 (info.seq_len bases)
+  int num_thr;                // tids of the consensus
+  const uint64_t *tid_seq;    // host: num_thr + 1 offsets into refc (tid t holds [tid_seq[t], tid_seq[t + 1]))
 };
 int encoder_view(spring_encoder_ctx *ctx, EncoderView *v);   // fails unless the context holds an encode
 

@@ -29,6 +29,7 @@
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_streams.h"
+#include "streams_internal.h"
 
 using sr::fail;
 
@@ -355,6 +356,8 @@ struct spring_streams_ctx {
   spring_streams_info info;
   DBuf out[SPRING_STREAMS_NUM];
   std::vector<uint64_t> table;   // SPRING_STREAMS_NUM x (num_blocks + 1)
+  uint32_t num_reads = 0, num_reads_per_block = 0;   // parameters of the last run (streams_view)
+  bool pe = false, po = false;
 };
 
 namespace {
@@ -508,6 +511,10 @@ int run_core(spring_streams_ctx *ctx, const In &I, uint32_t N, bool pe, bool po,
   float ms = 0;
   HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
   R.ms_device = ms;
+  ctx->num_reads = N;
+  ctx->num_reads_per_block = B;
+  ctx->pe = pe;
+  ctx->po = po;
   ctx->have = true;
   if (info_out) *info_out = R;
   return 0;
@@ -642,6 +649,22 @@ int spring_streams_download(spring_streams_ctx *ctx, int32_t stream_id, uint8_t 
 }
 
 }  // extern "C"
+
+namespace sr {
+int streams_view(spring_streams_ctx *ctx, StreamsView *v) {
+  if (!ctx || !v) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  if (!ctx->have) return fail(SPRING_REORDER_E_STATE, "no streams computed yet");
+  v->dev = ctx->dev;
+  v->info = ctx->info;
+  for (int s = 0; s < SPRING_STREAMS_NUM; s++) v->bytes[s] = ctx->out[s].as<uint8_t>();
+  v->table = ctx->table.data();
+  v->num_reads = ctx->num_reads;
+  v->num_reads_per_block = ctx->num_reads_per_block;
+  v->paired_end = ctx->pe;
+  v->preserve_order = ctx->po;
+  return 0;
+}
+}  // namespace sr
 
 // ------------------------------------------------------------------ file contract
 namespace {
