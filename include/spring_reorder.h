@@ -95,6 +95,10 @@ typedef struct {
                              on one GPU as in a pool, so that the choice never depends on the number of ranks */
   int32_t known_absent;   /* four-chain round kernel, reads up to 192 bases: chains remember which windows of their consensus
                              are known absent from the dictionaries and skip them (the table is immutable).  0 = on, -1 = off */
+  int32_t sort_prefix_bits; /* dictionary build: the radix sort orders the top T bits of the key hashes and an exact repair pass
+                             re-orders the runs where two keys share them (same result as the full sort).  0 = the library's
+                             choice, 64 = the full 64-bit sort, small values force the repair and its
+                             fall-back (tests).  Anything outside 0 .. 64 is refused by spring_reorder_create */
 } spring_reorder_opts;
 
 typedef struct {
@@ -123,6 +127,11 @@ typedef struct {
   uint64_t phases;         /* chain groups the chain phase ran with (opts.phases, or the library's choice) */
   double ms_search_busy;   /* time_search = 1: the time during which at least one round kernel was running (the union of the
                               launches' intervals); = ms_search_kernel unless two chain groups run side by side (phases = 2) */
+  uint64_t sort_prefix_bits;   /* dictionary build: bits of the key hash the radix sort ordered (last dictionary built) */
+  uint64_t sort_repaired_runs; /* ... runs of one prefix holding several keys that the repair pass re-ordered in place */
+  uint64_t sort_full_sorts;    /* ... dictionaries that were sorted again over all 64 bits (run too long, or too many runs) */
+  uint64_t sort_long_runs;     /* ... of those: because a run holding several keys was longer than the repair takes (1 024 entries) */
+  uint64_t sort_list_overflows;/* ... of those: because more hash changes inside runs were found than the repair's list holds */
 } spring_reorder_stats;
 
 void spring_reorder_default_opts(spring_reorder_opts *o);
@@ -166,7 +175,13 @@ int spring_reorder_load_dna(spring_reorder_ctx *ctx, const uint8_t *dna, size_t 
 
 /* Same, but the record stream is already resident in HBM (d_dna is a device
  * pointer the caller owns; fixed_len != 0 promises every record has
- * len == max_readlen so record i starts at i*(2+ceil(L/4))). */
+ * len == max_readlen so record i starts at i*(2+ceil(L/4))).  With fixed_len
+ * the unpack kernel fetches whole aligned 16-byte pieces: it also READS (never
+ * writes) up to 15 bytes below d_dna and up to 15 bytes past the last record,
+ * inside the 16-byte-aligned pieces that hold the first and the last byte of the
+ * stream -- the same memory page, so any device pointer is fine.  A length field
+ * above max_readlen is not checked here (the promise); the kernel then takes the
+ * record's own ceil(L/4) bytes and no more. */
 int spring_reorder_load_dna_device(spring_reorder_ctx *ctx, const void *d_dna, size_t nbytes, uint32_t n,
                                    uint32_t max_readlen, int32_t fixed_len);
 

@@ -226,19 +226,33 @@ struct DevParams {
 };
 
 // launchers (reorder_kernels.hip)
+constexpr int UNPACK_READS = 128;    // reads per block of k_unpack_fixed (fixed-size records, off == nullptr)
 void launch_unpack(hipStream_t st, const uint8_t *dna, const uint64_t *off, uint32_t n, int L, int W, int S,
                    uint32_t rec_fixed, uint64_t *reads, uint16_t *lens, uint32_t *bad_len = nullptr);
 void launch_flag_in_dict(hipStream_t st, const uint16_t *lens, uint32_t n, int dend, uint32_t *flag);
 void launch_keys(hipStream_t st, const uint64_t *reads, const uint16_t *lens, const uint32_t *slot, uint32_t n,
                  int S, int dstart, int dend, uint64_t *keys, uint32_t *vals);
+void launch_keys2(hipStream_t st, const uint64_t *reads, uint32_t n, int S, int dstart0, int dend0, int dstart1, int dend1,
+                  uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32_t *vals1);
+// exact repair after a stable sort of the top prefix_bits bits only (k_sort_breaks / k_sort_runs / k_sort_fix):
+// list, runs: cap entries; ctr: 4 words, zeroed.  Afterwards ctr[0] > cap or ctr[2] != 0 mean "not repaired: sort all
+// 64 bits", otherwise ctr[1] runs were re-ordered in place and (k, ids) equal the full stable sort.
+constexpr int SORT_FIX_MAX = 1024;   // longest run k_sort_fix re-orders (entries of one prefix)
+void launch_sort_repair(hipStream_t st, uint64_t *k, uint32_t *ids, uint64_t m, unsigned prefix_bits, uint32_t *list,
+                        uint32_t cap, uint32_t *ctr, uint2 *runs);
 // unique keys of both dictionaries merged by hash (mval = dict << 63 | index of the key in its dictionary)
 struct DictBuild {
   const uint32_t *ustart, *ucount, *ids;
   ulonglong2 *urec;
   uint32_t *deep, *ndeep;   // ndeep[0] bins listed in deep[], ndeep[1] reads in bins of >= BIG_BIN entries, ndeep[2] ... of >= MID_BIN
 };
+// pass 0: native pairs; the pairs of rank >= 4 go to the list ovf (ovf[0] = count, must be zero; indices from ovf + 1,
+// room for nmerged of them)
 void launch_tab_insert(hipStream_t st, const uint64_t *mhash, const uint64_t *mval, uint64_t nmerged, DictBuild d0,
-                       DictBuild d1, uint32_t *fpt, int bshift);
+                       DictBuild d1, uint32_t *fpt, int bshift, uint32_t *ovf);
+// pass 1 over the novf listed pairs
+void launch_tab_overflow(hipStream_t st, const uint64_t *mhash, const uint64_t *mval, uint64_t nmerged, DictBuild d0,
+                         DictBuild d1, uint32_t *fpt, int bshift, uint32_t *ovf, uint32_t novf);
 // minimizer-addressed table: bucket + {tag, payload} word of every merged entry (also writes the bin records), then,
 // after a sort by bucket, the two insert passes
 void launch_minz_prepare(hipStream_t st, const uint64_t *mhash, const uint64_t *mval, uint64_t nmerged, DictBuild d0,
@@ -247,8 +261,9 @@ void launch_tab_insert_minz(hipStream_t st, const uint32_t *bucket_sorted, const
                             uint32_t *fpt, int bshift, uint32_t *marked);
 hipError_t sort_pairs_u32_u64(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint32_t *kin, uint32_t *kout,
                               const uint64_t *vin, uint64_t *vout, size_t n, unsigned end_bit);
+// (the merged values are made on the fly: index of the key in its dictionary, | tag1 for those of k1)
 hipError_t merge_by_hash(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint64_t *k0, const uint64_t *k1,
-                         const uint64_t *v0, const uint64_t *v1, uint64_t *kout, uint64_t *vout, size_t n0, size_t n1);
+                         uint64_t tag1, uint64_t *kout, uint64_t *vout, size_t n0, size_t n1);
 void launch_iota_tag(hipStream_t st, uint64_t *v, uint64_t n, uint64_t tag);
 void launch_build_epos(hipStream_t st, const uint32_t *ids, uint64_t m, uint32_t *epos);
 void launch_trim_bins(hipStream_t st, const uint32_t *deep, const uint32_t *ndeep, uint32_t ndeep_host,
@@ -294,7 +309,7 @@ hipError_t reduce_max_u32(hipStream_t st, void *tmp, size_t &tmp_bytes, const ui
 hipError_t reduce_min_u32(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint32_t *in, uint32_t *out, size_t n);
 
 hipError_t sort_pairs(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint64_t *kin, uint64_t *kout,
-                      const uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit);
+                      const uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit, unsigned begin_bit = 0);
 hipError_t rle(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint64_t *in, size_t n, uint64_t *uniq,
                uint32_t *counts, uint32_t *nruns);
 hipError_t excl_scan_u32(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint32_t *in, uint32_t *out, size_t n);

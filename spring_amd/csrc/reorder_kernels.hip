@@ -270,6 +270,64 @@ __global__ void k_unpack(const uint8_t *__restrict__ dna, const uint64_t *__rest
   reads[i * S + j] = v;
 }
 
+// The same for a stream of fixed-size records (off == nullptr; 40 bytes at 150 bases): the records of a block's
+// UNPACK_READS reads are contiguous, so the block fetches them with coalesced 16-byte loads into LDS -- from the
+// 16-byte boundary below its first record: neither the record size nor the caller's base pointer need be a multiple
+// of 16, and an aligned 16-byte load that holds one byte of the stream never leaves that byte's page -- and then
+// every thread assembles two limbs per 16-byte store (the zero limbs j >= W ride along), the lengths go out in pairs.
+// A length field > L without bad_len reads at most the record's own bytes (k_unpack would run on into the next one).
+__global__ __launch_bounds__(256) void k_unpack_fixed(const uint8_t *__restrict__ dna, uint32_t n, int L, int W, int lgS,
+                                                      uint32_t rec, uint64_t *__restrict__ reads,
+                                                      uint16_t *__restrict__ lens, uint32_t *__restrict__ bad_len) {
+  extern __shared__ uint4 s_unpack[];
+  const uint32_t r0 = blockIdx.x * (uint32_t)UNPACK_READS;
+  const uint32_t nr = min((uint32_t)UNPACK_READS, n - r0);
+  const uint8_t *g = dna + (uint64_t)r0 * rec;
+  const uint32_t sh = (uint32_t)((uintptr_t)g & 15u);
+  const uint4 *ga = reinterpret_cast<const uint4 *>(g - sh);
+  const uint32_t nchunk = (sh + nr * rec + 15u) >> 4;
+  for (uint32_t k = threadIdx.x; k < nchunk; k += 256) s_unpack[k] = ga[k];
+  __syncthreads();
+  const uint8_t *sb = reinterpret_cast<const uint8_t *>(s_unpack);
+  const uint32_t *sw = reinterpret_cast<const uint32_t *>(s_unpack);
+  const bool chk = bad_len != nullptr;
+  auto len_of = [&](uint32_t r) -> uint32_t {
+    const uint32_t p = sh + r * rec;
+    return (uint32_t)sb[p] | ((uint32_t)sb[p + 1] << 8);
+  };
+  auto limb = [&](uint32_t m) -> uint64_t {
+    const uint32_t r = m >> lgS, j = m & ((1u << lgS) - 1u);
+    if ((int)j >= W) return 0;
+    uint32_t len = len_of(r);
+    if (chk && len != (uint32_t)L) len = (uint32_t)L;  // (stay inside the record; the result is discarded)
+    const uint32_t nb = min((len + 3u) / 4u, rec - 2u), pos = 8u * j;
+    if (pos >= nb) return 0;
+    const uint32_t p = sh + r * rec + 2u + pos, k = p >> 2, s8 = (p & 3u) * 8u;
+    uint64_t v = (uint64_t)sw[k] | ((uint64_t)sw[k + 1] << 32);
+    if (s8) v = (v >> s8) | ((uint64_t)sw[k + 2] << (64u - s8));
+    if (nb - pos < 8u) v &= (1ull << (8u * (nb - pos))) - 1ull;
+    return v;
+  };
+  for (uint32_t t = threadIdx.x; 2u * t < nr; t += 256) {
+    const uint32_t r = 2u * t;
+    uint32_t l0 = len_of(r), l1 = r + 1 < nr ? len_of(r + 1) : (uint32_t)L;
+    if (chk && (l0 != (uint32_t)L || l1 != (uint32_t)L)) {
+      *bad_len = 1u;
+      l0 = l1 = (uint32_t)L;
+    }
+    if (r + 1 < nr) *reinterpret_cast<uint32_t *>(lens + r0 + r) = l0 | (l1 << 16);
+    else lens[r0 + r] = (uint16_t)l0;
+  }
+  const uint32_t nl = nr << lgS;
+  uint64_t *out = reads + ((uint64_t)r0 << lgS);
+  for (uint32_t q = threadIdx.x; 2u * q < nl; q += 256) {
+    const uint32_t m = 2u * q;
+    const uint64_t v0 = limb(m);
+    if (m + 1 < nl) *reinterpret_cast<ulonglong2 *>(out + m) = make_ulonglong2(v0, limb(m + 1));
+    else out[m] = v0;
+  }
+}
+
 // ------------------------------------------------ K2 key extraction (bitset_util.h:83-105)
 __global__ void k_flag_in_dict(const uint16_t *__restrict__ lens, uint32_t n, int dend,
                                uint32_t *__restrict__ flag) {
@@ -293,6 +351,98 @@ __global__ void k_keys(const uint64_t *__restrict__ reads, const uint16_t *__res
   keys[o] = mix64(v);  // the dictionary is sorted by hash: equal keys stay adjacent, buckets come out in order
   vals[o] = i;
 }
+// both dictionaries' pairs from one pass over the reads (pools of one read length: every read is in both, slot = id)
+__global__ void k_keys2(const uint64_t *__restrict__ reads, uint32_t n, int S, int dstart0, int klen0, int dstart1,
+                        int klen1, uint64_t *__restrict__ keys0, uint32_t *__restrict__ vals0,
+                        uint64_t *__restrict__ keys1, uint32_t *__restrict__ vals1) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t *r = reads + (uint64_t)i * S;
+  keys0[i] = mix64(read_window(r, S, dstart0, 2 * klen0));
+  vals0[i] = i;
+  keys1[i] = mix64(read_window(r, S, dstart1, 2 * klen1));
+  vals1[i] = i;
+}
+
+// ------------------------------------------------ prefix sort: exact repair
+// The dictionary sort orders only the top T bits of the hashes (stable, so a run = the entries of one prefix comes out
+// in read-id order).  A run is final unless it holds two different hashes; then it must be ordered by (hash, id).
+// k_sort_breaks lists every position whose hash differs from its predecessor's inside a run (one compare per element);
+// k_sort_runs, one wavefront per listed position, keeps the first of each run, finds the run's ends 64 entries at a
+// time and lists {start, length}; k_sort_fix, one wavefront per listed run, ranks the run's entries in LDS and writes
+// them back in place.  ctr: [0] positions found (may exceed the list: the host then sorts all 64 bits), [1] runs
+// listed, [2] set when a run is longer than SORT_FIX_MAX (same consequence).
+__global__ void k_sort_breaks(const uint64_t *__restrict__ k, uint64_t m, int shift, uint32_t *__restrict__ list,
+                              uint32_t cap, uint32_t *__restrict__ ctr) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0 || i >= m) return;
+  const uint64_t a = k[i - 1], b = k[i];
+  if (a != b && (a >> shift) == (b >> shift)) {
+    const uint32_t s = atomicAdd(ctr, 1u);
+    if (s < cap) list[s] = (uint32_t)i;
+  }
+}
+__global__ __launch_bounds__(256) void k_sort_runs(const uint64_t *__restrict__ k, uint64_t m, int shift,
+                                                   const uint32_t *__restrict__ list, uint32_t cap,
+                                                   uint32_t *__restrict__ ctr, uint2 *__restrict__ runs) {
+  const uint32_t nbr = ctr[0];
+  if (nbr > cap) return;
+  const uint32_t lane = threadIdx.x & 63u, nwaves = gridDim.x * 4u;
+  for (uint32_t c = blockIdx.x * 4u + (threadIdx.x >> 6); c < nbr; c += nwaves) {
+    const uint64_t i = list[c];
+    const uint64_t p = k[i] >> shift, prev = k[i - 1];
+    uint64_t s = 0, e = 0;
+    bool mine = true;  // is this the first hash change of its run?  (everything here is the same in all lanes)
+    for (uint64_t w = 2;; w += 64) {  // entries i - w - lane: back from i - 2 (i - 1 is in the run and holds prev)
+      const uint64_t o = w + lane;
+      const bool valid = o <= i;
+      const uint64_t v = valid ? k[i - o] : 0;
+      const bool inrun = valid && (v >> shift) == p;
+      const unsigned long long m_out = __ballot(!inrun), m_dif = __ballot(inrun && v != prev);
+      const int f_out = m_out ? __ffsll(m_out) - 1 : 64, f_dif = m_dif ? __ffsll(m_dif) - 1 : 64;
+      if (f_dif < f_out) { mine = false; break; }
+      if (f_out < 64) { s = i - (w + (uint64_t)f_out) + 1; break; }
+      if (w + 64 > (uint64_t)SORT_FIX_MAX) {
+        if (lane == 0) atomicOr(ctr + 2, 1u);
+        mine = false;
+        break;
+      }
+    }
+    if (!mine) continue;
+    for (uint64_t w = i + 1;; w += 64) {
+      const uint64_t x = w + lane;
+      const bool inrun = x < m && (k[x] >> shift) == p;
+      const unsigned long long m_out = __ballot(!inrun);
+      if (m_out) { e = w + (uint64_t)(__ffsll(m_out) - 1); break; }
+      if (w + 64 - s > (uint64_t)SORT_FIX_MAX) { e = w + 64; break; }
+    }
+    if (e - s > (uint64_t)SORT_FIX_MAX) {
+      if (lane == 0) atomicOr(ctr + 2, 1u);
+      continue;
+    }
+    if (lane == 0) runs[atomicAdd(ctr + 1, 1u)] = make_uint2((uint32_t)s, (uint32_t)(e - s));
+  }
+}
+__global__ __launch_bounds__(64) void k_sort_fix(uint64_t *__restrict__ k, uint32_t *__restrict__ ids, uint32_t cap,
+                                                 const uint32_t *__restrict__ ctr, const uint2 *__restrict__ runs) {
+  __shared__ uint64_t sk[SORT_FIX_MAX];
+  __shared__ uint32_t sv[SORT_FIX_MAX];
+  if (ctr[0] > cap || ctr[2]) return;  // (the host sorts this dictionary again, all 64 bits)
+  const uint32_t nruns = ctr[1];
+  for (uint32_t c = blockIdx.x; c < nruns; c += gridDim.x) {
+    const uint2 rn = runs[c];
+    for (uint32_t x = threadIdx.x; x < rn.y; x += 64) { sk[x] = k[(uint64_t)rn.x + x]; sv[x] = ids[(uint64_t)rn.x + x]; }
+    __syncthreads();
+    for (uint32_t x = threadIdx.x; x < rn.y; x += 64) {
+      const uint64_t h = sk[x];
+      uint32_t rank = 0;
+      for (uint32_t y = 0; y < rn.y; y++) rank += (sk[y] < h || (sk[y] == h && y < x)) ? 1u : 0u;
+      k[(uint64_t)rn.x + rank] = h;
+      ids[(uint64_t)rn.x + rank] = sv[x];
+    }
+    __syncthreads();
+  }
+}
 
 // ------------------------------------------------ K3 table insert (bitset_util.h:122-217)
 // one thread per unique (key, dictionary) pair; the pairs of both dictionaries arrive merged by hash = by
@@ -302,16 +452,28 @@ __global__ void k_keys(const uint64_t *__restrict__ reads, const uint16_t *__res
 // of rank >= 4 (under 1 % at load 0.2) claim the next free slot further on with CAS, after pass 0 has placed
 // all native pairs.  A lookup scans slots in order and stops at the first empty one, so which free slot an
 // overflow pair gets does not matter.
+// Pass 0 hands the overflow pairs over in a list (ovf[0] = how many, ovf + 1 = their indices; room for every pair, so
+// the list cannot run over), and pass 1 runs over those few only.
 template <bool OVERFLOW>
 __global__ void k_tab_insert(const uint64_t *__restrict__ mhash, const uint64_t *__restrict__ mval, uint64_t nm,
-                             DictBuild d0, DictBuild d1, uint32_t *fpt, int bshift) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nm) return;
+                             DictBuild d0, DictBuild d1, uint32_t *fpt, int bshift, uint32_t *ovf) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int rank = 4;
+  if (OVERFLOW) {
+    if (i >= ovf[0]) return;
+    i = ovf[1 + i];
+  } else {
+    if (i >= nm) return;
+    const uint64_t bi = bucket_of(mhash[i], bshift);
+    rank = 0;
+    while (rank < 4 && i > (uint64_t)rank && bucket_of(mhash[i - 1 - rank], bshift) == bi) rank++;
+    if (rank >= 4) {
+      ovf[1 + atomicAdd(ovf, 1u)] = (uint32_t)i;
+      return;
+    }
+  }
   const uint64_t h = mhash[i];
   const uint64_t b0 = bucket_of(h, bshift);
-  int rank = 0;
-  while (rank < 4 && i > (uint64_t)rank && bucket_of(mhash[i - 1 - rank], bshift) == b0) rank++;
-  if (OVERFLOW != (rank >= 4)) return;
   const uint64_t mv = mval[i];
   const uint32_t l = (uint32_t)(mv >> 63), u = (uint32_t)mv;
   const DictBuild &d = l ? d1 : d0;
@@ -3109,6 +3271,13 @@ __global__ void k_synth(uint8_t *__restrict__ dst, uint32_t n, uint32_t L, uint6
 void launch_unpack(hipStream_t st, const uint8_t *dna, const uint64_t *off, uint32_t n, int L, int W, int S,
                    uint32_t rec_fixed, uint64_t *reads, uint16_t *lens, uint32_t *bad_len) {
   if (!n) return;
+  if (!off && !((uintptr_t)reads & 15u) && !((uintptr_t)lens & 3u)) {  // fixed-size records: wide loads and stores
+    int lgS = 0;
+    while ((1 << lgS) < S) lgS++;
+    const size_t lds = ((size_t)UNPACK_READS * rec_fixed + 15 + 12 + 15) / 16 * 16;
+    hipLaunchKernelGGL(k_unpack_fixed, GRID1(n, UNPACK_READS), dim3(256), lds, st, dna, n, L, W, lgS, rec_fixed, reads, lens, bad_len);
+    return;
+  }
   uint64_t tot = (uint64_t)n * S;
   hipLaunchKernelGGL(k_unpack, GRID1(tot, 256), dim3(256), 0, st, dna, off, n, L, W, S, rec_fixed, reads, lens, bad_len);
 }
@@ -3119,11 +3288,27 @@ void launch_keys(hipStream_t st, const uint64_t *reads, const uint16_t *lens, co
                  int S, int dstart, int dend, uint64_t *keys, uint32_t *vals) {
   hipLaunchKernelGGL(k_keys, GRID1(n, 256), dim3(256), 0, st, reads, lens, slot, n, S, dstart, dend, keys, vals);
 }
+void launch_keys2(hipStream_t st, const uint64_t *reads, uint32_t n, int S, int dstart0, int dend0, int dstart1, int dend1,
+                  uint64_t *keys0, uint32_t *vals0, uint64_t *keys1, uint32_t *vals1) {
+  hipLaunchKernelGGL(k_keys2, GRID1(n, 256), dim3(256), 0, st, reads, n, S, dstart0, dend0 - dstart0 + 1, dstart1,
+                     dend1 - dstart1 + 1, keys0, vals0, keys1, vals1);
+}
+void launch_sort_repair(hipStream_t st, uint64_t *k, uint32_t *ids, uint64_t m, unsigned prefix_bits, uint32_t *list,
+                        uint32_t cap, uint32_t *ctr, uint2 *runs) {
+  const int shift = 64 - (int)prefix_bits;
+  hipLaunchKernelGGL(k_sort_breaks, GRID1(m, 256), dim3(256), 0, st, k, m, shift, list, cap, ctr);
+  hipLaunchKernelGGL(k_sort_runs, dim3(1024), dim3(256), 0, st, k, m, shift, list, cap, ctr, runs);
+  hipLaunchKernelGGL(k_sort_fix, dim3(4096), dim3(64), 0, st, k, ids, cap, ctr, runs);
+}
 void launch_tab_insert(hipStream_t st, const uint64_t *mhash, const uint64_t *mval, uint64_t nmerged, DictBuild d0,
-                       DictBuild d1, uint32_t *fpt, int bshift) {
+                       DictBuild d1, uint32_t *fpt, int bshift, uint32_t *ovf) {
   if (!nmerged) return;
-  hipLaunchKernelGGL(k_tab_insert<false>, GRID1(nmerged, 256), dim3(256), 0, st, mhash, mval, nmerged, d0, d1, fpt, bshift);
-  hipLaunchKernelGGL(k_tab_insert<true>, GRID1(nmerged, 256), dim3(256), 0, st, mhash, mval, nmerged, d0, d1, fpt, bshift);
+  hipLaunchKernelGGL(k_tab_insert<false>, GRID1(nmerged, 256), dim3(256), 0, st, mhash, mval, nmerged, d0, d1, fpt, bshift, ovf);
+}
+void launch_tab_overflow(hipStream_t st, const uint64_t *mhash, const uint64_t *mval, uint64_t nmerged, DictBuild d0,
+                         DictBuild d1, uint32_t *fpt, int bshift, uint32_t *ovf, uint32_t novf) {
+  if (!novf) return;
+  hipLaunchKernelGGL(k_tab_insert<true>, GRID1(novf, 256), dim3(256), 0, st, mhash, mval, nmerged, d0, d1, fpt, bshift, ovf);
 }
 void launch_minz_prepare(hipStream_t st, const uint64_t *mhash, const uint64_t *mval, uint64_t nmerged, DictBuild d0,
                          DictBuild d1, int lshift, uint32_t *bucket, uint64_t *tagpay) {
@@ -3335,8 +3520,15 @@ void launch_synth(hipStream_t st, uint8_t *dst, uint32_t n, uint32_t L, uint64_t
 
 // ------------------------------------------------- rocPRIM plumbing (sort / RLE / scan)
 hipError_t sort_pairs(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint64_t *kin, uint64_t *kout,
-                      const uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit) {
-  return rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, 0u, end_bit, st);
+                      const uint32_t *vin, uint32_t *vout, size_t n, unsigned end_bit, unsigned begin_bit) {
+  // A bit range that ends at bit 64 and does not start at bit 0 must stay off rocPRIM's merge-sort path (rocPRIM 4.2.0,
+  // ROCm 7.2: device/detail/device_radix_sort.hpp, radix_merge_compare; drop this once that is fixed; its choice up
+  // to 2^20 items): that path's comparator builds its mask from T(1) << (begin_bit + bits), a shift by the key's whole
+  // width, and then compares the bits BELOW begin_bit.  Merge-sort limit 0 = block sort up to one block, one-sweep beyond.
+  if (begin_bit != 0)
+    return rocprim::radix_sort_pairs<rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config, rocprim::default_config, 0>>(
+        tmp, tmp_bytes, kin, kout, vin, vout, n, begin_bit, end_bit, st);
+  return rocprim::radix_sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, n, begin_bit, end_bit, st);
 }
 hipError_t sort_pairs_u32_u64(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint32_t *kin, uint32_t *kout,
                               const uint64_t *vin, uint64_t *vout, size_t n, unsigned end_bit) {
@@ -3347,8 +3539,10 @@ hipError_t rle(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint64_t *in,
   return rocprim::run_length_encode(tmp, tmp_bytes, in, n, uniq, counts, nruns, st);
 }
 hipError_t merge_by_hash(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint64_t *k0, const uint64_t *k1,
-                         const uint64_t *v0, const uint64_t *v1, uint64_t *kout, uint64_t *vout, size_t n0, size_t n1) {
-  return rocprim::merge(tmp, tmp_bytes, k0, k1, kout, v0, v1, vout, n0, n1, rocprim::less<uint64_t>(), st);
+                         uint64_t tag1, uint64_t *kout, uint64_t *vout, size_t n0, size_t n1) {
+  // values: the key's index in its dictionary (| tag1 for the second one's), counted on the fly
+  return rocprim::merge(tmp, tmp_bytes, k0, k1, kout, rocprim::counting_iterator<uint64_t>(0),
+                        rocprim::counting_iterator<uint64_t>(tag1), vout, n0, n1, rocprim::less<uint64_t>(), st);
 }
 hipError_t excl_scan_u32(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint32_t *in, uint32_t *out, size_t n) {
   return rocprim::exclusive_scan(tmp, tmp_bytes, in, out, 0u, n, rocprim::plus<uint32_t>(), st);

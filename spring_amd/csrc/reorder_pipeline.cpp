@@ -366,6 +366,8 @@ int spring_reorder_create(spring_reorder_ctx **out, const spring_reorder_opts *o
   spring_reorder_opts o;
   if (opts) o = *opts; else spring_reorder_default_opts(&o);
   if (o.num_thr <= 0) return fail(SPRING_REORDER_E_ARG, "num_thr must be >= 1");
+  if (o.sort_prefix_bits < 0 || o.sort_prefix_bits > 64)
+    return fail(SPRING_REORDER_E_ARG, "sort_prefix_bits: 0 (library's choice) or 1 .. 64 bits of the key hash (64 = the full sort)");
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (ndev <= 0) return fail(SPRING_REORDER_E_HIP, "no HIP device");
@@ -1035,6 +1037,11 @@ static TabView tab_view(const spring_reorder_ctx *ctx) {
   return t;
 }
 
+// Bits of the hash the dictionary sort orders (opts.sort_prefix_bits = 0).  With m keys and a T-bit
+// prefix about m^2 / 2^(T+1) pairs of distinct keys share a prefix: 4.5 k at 100 M reads and T = 40, 73 k at 400 M -- a
+// handful of short runs for the repair -- where T = 32 would leave 1.2 M / 18.6 M.  rocPRIM sorts 8 bits per pass here.
+static unsigned sort_prefix_auto(uint64_t m) { return m <= (1ull << 29) ? 40u : 48u; }
+
 int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
   double t_last = now_ms();
   if (!ctx) return fail(SPRING_REORDER_E_ARG, "ctx is NULL");
@@ -1046,6 +1053,12 @@ int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
   HIPCHK(hipEventRecord(ctx->ev[2], st));
   uint64_t *uhash[2] = {nullptr, nullptr};          // sorted unique mix64(key) per dictionary
   uint32_t *ustart[2] = {nullptr, nullptr}, *ucount[2] = {nullptr, nullptr};
+  // pools of one read length: every read is in both dictionaries, and one pass over the reads serves both
+  const bool both_dense = n && ctx->uniform && ctx->L > ctx->dict[0].end && ctx->L > ctx->dict[1].end;
+  uint64_t *keys_both[2] = {nullptr, nullptr};
+  uint32_t *vals_both[2] = {nullptr, nullptr};
+  ctx->stats.sort_repaired_runs = 0; ctx->stats.sort_full_sorts = 0; ctx->stats.sort_prefix_bits = 0;
+  ctx->stats.sort_long_runs = 0; ctx->stats.sort_list_overflows = 0;
   for (int l = 0; l < 2; l++) {
     DictDev &d = ctx->dict[l];
     uint32_t m = 0;
@@ -1082,24 +1095,70 @@ int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
       if (d_flag) { ctx->dfree(d_flag); ctx->dfree(d_slot); }
       continue;
     }
-    uint64_t *k_in = nullptr, *k_out = nullptr;
-    uint32_t *v_in = nullptr, *cnt = nullptr, *d_nruns = nullptr;
-    DMALLOC(k_in, (size_t)m * 8);
+    uint64_t *k_in = keys_both[l], *k_out = nullptr;
+    uint32_t *v_in = vals_both[l], *cnt = nullptr, *d_nruns = nullptr;
+    if (!k_in) {
+      DMALLOC(k_in, (size_t)m * 8);
+      DMALLOC(v_in, (size_t)m * 4);
+    }
     DMALLOC(k_out, (size_t)m * 8);
-    DMALLOC(v_in, (size_t)m * 4);
     DMALLOC(d.ids, (size_t)m * 4);
     DBG_T("alloc keys");
-    launch_keys(st, ctx->d_reads, ctx->d_lens, ctx->uniform ? nullptr : d_slot, n, ctx->S, d.start, d.end, k_in, v_in);
+    if (l == 0 && both_dense) {  // one pass over the reads emits the pairs of both dictionaries
+      DMALLOC(keys_both[1], (size_t)n * 8);
+      DMALLOC(vals_both[1], (size_t)n * 4);
+      launch_keys2(st, ctx->d_reads, n, ctx->S, d.start, d.end, ctx->dict[1].start, ctx->dict[1].end, k_in, v_in,
+                   keys_both[1], vals_both[1]);
+    } else if (!keys_both[l]) {
+      launch_keys(st, ctx->d_reads, ctx->d_lens, ctx->uniform ? nullptr : d_slot, n, ctx->S, d.start, d.end, k_in, v_in);
+    }
     HIPCHK(hipGetLastError());
     DBG_T("k_keys");
-    const unsigned end_bit = 64;  // k_keys emits mix64(key): all 64 bits are significant
-    // stable LSD radix sort: equal keys (equal hashes: mix64 is a bijection) keep ascending read id
-    // (bitset_util.h:192-210), and the unique keys come out in bucket order for k_tab_insert
-    tmp_bytes = 0;
-    HIPCHK(sort_pairs(st, nullptr, tmp_bytes, k_in, k_out, v_in, d.ids, m, end_bit));
-    DMALLOC(d_tmp, tmp_bytes);
-    HIPCHK(sort_pairs(st, d_tmp, tmp_bytes, k_in, k_out, v_in, d.ids, m, end_bit));
-    DBG_T("sort");
+    // k_keys emits mix64(key): all 64 bits are significant.  The result is the stable sort by all of them: equal keys
+    // (equal hashes: mix64 is a bijection) keep ascending read id (bitset_util.h:192-210), and the unique keys come out
+    // in bucket order for k_tab_insert.  Only the top bits carry order anything depends on -- the rest keeps apart the
+    // rare distinct keys that share a prefix -- so the radix sort runs over the top T bits (5 digit passes instead of
+    // 8 at T = 40) and the few runs of one prefix that hold two hashes are re-ordered afterwards (launch_sort_repair).
+    // A run too long for that, or too many of them: this dictionary is sorted again over all 64 bits.
+    const unsigned T = ctx->o.sort_prefix_bits > 0 ? (unsigned)ctx->o.sort_prefix_bits : sort_prefix_auto(m);
+    ctx->stats.sort_prefix_bits = T;
+    bool full = T >= 64;
+    if (!full) {
+      uint32_t *d_ctr = nullptr, *d_list = nullptr;
+      uint2 *d_runs = nullptr;
+      const uint32_t cap = m / 4 + 1024;
+      DMALLOC(d_ctr, 16);
+      DMALLOC(d_list, (size_t)cap * 4);
+      DMALLOC(d_runs, (size_t)cap * 8);
+      HIPCHK(hipMemsetAsync(d_ctr, 0, 16, st));
+      tmp_bytes = 0;
+      HIPCHK(sort_pairs(st, nullptr, tmp_bytes, k_in, k_out, v_in, d.ids, m, 64, 64 - T));
+      DMALLOC(d_tmp, tmp_bytes);
+      HIPCHK(sort_pairs(st, d_tmp, tmp_bytes, k_in, k_out, v_in, d.ids, m, 64, 64 - T));
+      DBG_T("prefix sort");
+      launch_sort_repair(st, k_out, d.ids, m, T, d_list, cap, d_ctr, d_runs);
+      HIPCHK(hipGetLastError());
+      uint32_t ctr[4] = {0, 0, 0, 0};
+      HIPCHK(hipMemcpyAsync(ctr, d_ctr, 16, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      full = ctr[0] > cap || ctr[2] != 0;
+      if (ctr[0] > cap) ctx->stats.sort_list_overflows++;
+      else if (ctr[2]) ctx->stats.sort_long_runs++;
+      if (!full) ctx->stats.sort_repaired_runs += ctr[1];
+      if (dbg) fprintf(stderr, "[dict] prefix bits %u: %u hash changes inside runs, %u runs re-ordered%s\n", T, ctr[0], ctr[1],
+                       full ? " -- not repairable in place: full sort" : "");
+      ctx->dfree(d_tmp); d_tmp = nullptr;
+      ctx->dfree(d_ctr); ctx->dfree(d_list); ctx->dfree(d_runs);
+      DBG_T("sort repair");
+    }
+    if (full) {
+      if (T < 64) ctx->stats.sort_full_sorts++;
+      tmp_bytes = 0;
+      HIPCHK(sort_pairs(st, nullptr, tmp_bytes, k_in, k_out, v_in, d.ids, m, 64));
+      DMALLOC(d_tmp, tmp_bytes);
+      HIPCHK(sort_pairs(st, d_tmp, tmp_bytes, k_in, k_out, v_in, d.ids, m, 64));
+      DBG_T("sort");
+    }
     ctx->dfree(d_tmp); d_tmp = nullptr;
     ctx->dfree(v_in);
     // unique keys + run lengths (bitset_util.h:122-127), reuse k_in for the unique keys
@@ -1156,24 +1215,22 @@ int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
   uint32_t *const tab_words = reinterpret_cast<uint32_t *>(ctx->fpt);
   DBG_T("alloc+memset tab");
   if (nm) {
-    uint64_t *mv0 = nullptr, *mv1 = nullptr, *mh = nullptr, *mv = nullptr;
+    uint64_t *mv0 = nullptr, *mh = nullptr, *mv = nullptr;
     void *d_tmp = nullptr;
-    DMALLOC(mv0, std::max<uint64_t>(nk0, 1) * 8);
-    DMALLOC(mv1, std::max<uint64_t>(nk1, 1) * 8);
-    launch_iota_tag(st, mv0, nk0, 0ull);
-    launch_iota_tag(st, mv1, nk1, 1ull << 63);
     const uint64_t *h_in = nullptr, *v_in = nullptr;
     if (nk0 && nk1) {
       DMALLOC(mh, nm * 8);
       DMALLOC(mv, nm * 8);
       size_t tb = 0;
-      HIPCHK(merge_by_hash(st, nullptr, tb, uhash[0], uhash[1], mv0, mv1, mh, mv, nk0, nk1));
+      HIPCHK(merge_by_hash(st, nullptr, tb, uhash[0], uhash[1], 1ull << 63, mh, mv, nk0, nk1));
       DMALLOC(d_tmp, tb);
-      HIPCHK(merge_by_hash(st, d_tmp, tb, uhash[0], uhash[1], mv0, mv1, mh, mv, nk0, nk1));
+      HIPCHK(merge_by_hash(st, d_tmp, tb, uhash[0], uhash[1], 1ull << 63, mh, mv, nk0, nk1));
       h_in = mh; v_in = mv;
-    } else {
+    } else {  // one dictionary is empty: the other's keys as they are, values = index | dictionary
+      DMALLOC(mv0, nm * 8);
+      launch_iota_tag(st, mv0, nm, nk0 ? 0ull : 1ull << 63);
       h_in = nk0 ? uhash[0] : uhash[1];
-      v_in = nk0 ? mv0 : mv1;
+      v_in = mv0;
     }
     DBG_T("merge");
     DictBuild db[2];
@@ -1182,12 +1239,23 @@ int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
       db[l].ustart = ustart[l]; db[l].ucount = ucount[l]; db[l].ids = d.ids; db[l].urec = d.urec;
       db[l].deep = d.deep; db[l].ndeep = d.d_ndeep;
     }
-    uint32_t *bk_in = nullptr, *bk_out = nullptr, *d_marked = nullptr;
+    uint32_t *bk_in = nullptr, *bk_out = nullptr, *d_marked = nullptr, *d_ovf = nullptr;
     uint64_t *tp_in = nullptr, *tp_out = nullptr;
     ctx->marked_lines = 0;
     void *d_tmp2 = nullptr;
     if (!ctx->minz) {
-      launch_tab_insert(st, h_in, v_in, nm, db[0], db[1], tab_words, ctx->bshift);
+      ctx->dfree(d_tmp); d_tmp = nullptr;  // (the merge's scratch makes room for the list of overflow pairs)
+      // list of the overflow pairs: 32-bit indices, room for every pair (a table for 2^32 pairs would not fit a device)
+      if (nm >= 0xffffffffull) return fail(SPRING_REORDER_E_ARG, "build_dict: %llu keys exceed the 32-bit index space of the table build", (unsigned long long)nm);
+      uint32_t novf = 0;
+      DMALLOC(d_ovf, ((size_t)nm + 1) * 4);
+      HIPCHK(hipMemsetAsync(d_ovf, 0, 4, st));
+      launch_tab_insert(st, h_in, v_in, nm, db[0], db[1], tab_words, ctx->bshift, d_ovf);
+      HIPCHK(hipMemcpyAsync(&novf, d_ovf, 4, hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      DBG_T("insert pass 0");
+      launch_tab_overflow(st, h_in, v_in, nm, db[0], db[1], tab_words, ctx->bshift, d_ovf, novf);
+      if (dbg) fprintf(stderr, "[dict] %u of %llu pairs overflow their bucket\n", novf, (unsigned long long)nm);
     } else {
       DMALLOC(bk_in, nm * 4); DMALLOC(bk_out, nm * 4);
       DMALLOC(tp_in, nm * 8); DMALLOC(tp_out, nm * 8);
@@ -1215,8 +1283,8 @@ int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
                      MID_BIN, nd[0][2], nd[1][2], BIG_BIN, nd[0][1], nd[1][1]);
     ctx->stats.table_marked_lines = ctx->marked_lines;
     DBG_T("insert");
-    ctx->dfree(mv0); ctx->dfree(mv1); ctx->dfree(mh); ctx->dfree(mv); ctx->dfree(d_tmp);
-    ctx->dfree(bk_in); ctx->dfree(bk_out); ctx->dfree(tp_in); ctx->dfree(tp_out); ctx->dfree(d_tmp2); ctx->dfree(d_marked);
+    ctx->dfree(mv0); ctx->dfree(mh); ctx->dfree(mv); ctx->dfree(d_tmp);
+    ctx->dfree(bk_in); ctx->dfree(bk_out); ctx->dfree(tp_in); ctx->dfree(tp_out); ctx->dfree(d_tmp2); ctx->dfree(d_marked); ctx->dfree(d_ovf);
   }
   for (int l = 0; l < 2; l++) { ctx->dfree(uhash[l]); ctx->dfree(ustart[l]); ctx->dfree(ucount[l]); }
   DBG_T("free temps");
