@@ -7,3 +7,4 @@ from .reorder import (CompressionParams, ReorderError, ReorderOpts, ReorderStage
                       synth_dna_host, synth_genome_host, SYNTH_GENOMIC, SYNTH_PAIRED, SYNTH_REPEATS)
 from .streams import StreamsStage, call_reorder_compress_streams  # noqa: F401,E402
 from .decode import DecodeStage  # noqa: F401,E402
+from .qualid import QualIdStage  # noqa: F401,E402

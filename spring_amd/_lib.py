@@ -38,6 +38,13 @@ DECODE_EXPORTS = [
     "spring_decode_download", "spring_decode_get_info",
 ]
 
+# include/spring_qualid.h: a list of its own as well
+QUALID_EXPORTS = [
+    "spring_qualid_create", "spring_qualid_destroy", "spring_qualid_order_from_host", "spring_qualid_order_from_encoder",
+    "spring_qualid_from_fastq", "spring_qualid_from_lines", "spring_qualid_download", "spring_qualid_get_info",
+    "spring_quality_table", "spring_id_pattern",
+]
+
 
 class Opts(C.Structure):
     _fields_ = [("device", C.c_int32), ("num_chains", C.c_uint32), ("num_thr", C.c_int32),
@@ -76,6 +83,18 @@ class StreamsInfo(C.Structure):
     _fields_ = ([("num_units", C.c_uint64), ("num_blocks", C.c_uint64), ("bytes", C.c_uint64 * STREAMS_NUM),
                  ("flag_count", C.c_uint64 * 5), ("pos_escapes", C.c_uint64), ("n_aligned", C.c_uint64),
                  ("ms_device", C.c_double), ("ms_file", C.c_double)])
+
+    def asdict(self):
+        d = {}
+        for k, _ in self._fields_:
+            v = getattr(self, k)
+            d[k] = list(v) if hasattr(v, "__len__") else v
+        return d
+
+
+class QualIdInfo(C.Structure):
+    _fields_ = [("num_units", C.c_uint64), ("num_blocks", C.c_uint64), ("bytes", C.c_uint64 * 2),
+                ("bytes_changed", C.c_uint64), ("max_len", C.c_uint32 * 2), ("ms_device", C.c_double)]
 
     def asdict(self):
         d = {}
@@ -226,6 +245,21 @@ def lib():
                                            C.c_uint32, C.POINTER(DecodeInfo)]
     L.spring_decode_download.argtypes = [vp, C.c_int32, vp, vp]
     L.spring_decode_get_info.argtypes = [vp, C.POINTER(DecodeInfo)]
+    L.spring_qualid_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.spring_qualid_destroy.argtypes = [vp]
+    L.spring_qualid_destroy.restype = None
+    L.spring_qualid_order_from_host.argtypes = [vp, vp, C.c_uint32, C.c_int32]
+    L.spring_qualid_order_from_encoder.argtypes = [vp, vp, C.c_uint32, C.c_int32]
+    L.spring_qualid_from_fastq.argtypes = [vp, u8p, C.c_size_t, C.c_int32, u8p, C.c_uint32, C.POINTER(QualIdInfo)]
+    L.spring_qualid_from_lines.argtypes = [vp, C.c_int32, u8p, C.c_size_t, u8p, C.c_uint32, C.POINTER(QualIdInfo)]
+    L.spring_qualid_download.argtypes = [vp, C.c_int32, u8p, vp, vp]
+    L.spring_qualid_get_info.argtypes = [vp, C.POINTER(QualIdInfo)]
+    L.spring_quality_table.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, u8p]
+    L.spring_id_pattern.argtypes = [u8p, C.c_size_t, u8p, C.c_size_t, C.c_int32, C.POINTER(C.c_uint8),
+                                    C.POINTER(C.c_double)]
+    for name in QUALID_EXPORTS:
+        if name != "spring_qualid_destroy":
+            getattr(L, name).restype = C.c_int
     for name in DECODE_EXPORTS:
         if name != "spring_decode_destroy":
             getattr(L, name).restype = C.c_int

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "spring_reorder.h"
 
 namespace sr {
@@ -65,6 +67,10 @@ int load_dna_source(spring_reorder_ctx *ctx, const DnaSource &src, uint32_t n, u
 int emit_dna_device(spring_reorder_ctx *ctx, int32_t tid, uint8_t **d_out, size_t *nbytes, uint64_t s_first = 0,
                     uint64_t s_cnt = ~0ull, size_t *mid_bytes = nullptr /* tid >= 0: byte offset of record tid_mid[tid] */);
 void emit_dna_free(spring_reorder_ctx *ctx, uint8_t *d);
+
+// A gzip'ed FASTQ image (magic 1f 8b) inflated on the host into buf, p / n redirected to it; anything else is left as
+// it is (reorder_pipeline.cpp; shared by the FASTQ front end and the quality / id stage).
+int gunzip_if_needed(const uint8_t *&p, size_t &n, std::vector<uint8_t> &buf);
 
 void mg_comm_abort(spring_mg_comm *c);  // a failed rank of an in-process pool unblocks its peers (ncclCommAbort)
 hipError_t dev_alloc(int dev, size_t bytes, void **out);     // pooled (reorder_pipeline.cpp)

@@ -781,7 +781,8 @@ static int fq_scan_file(spring_reorder_ctx *ctx, const uint8_t *txt, size_t nbyt
 // A gzip'ed FASTQ buffer (magic 1f 8b; preprocess.cpp:154-183 reads .gz input through
 // boost::iostreams::gzip_decompressor) is inflated on the host, every member of a multi-member file (bgzip,
 // concatenated .gz) in turn; anything else is taken as text.
-static int gunzip_if_needed(const uint8_t *&p, size_t &n, std::vector<uint8_t> &buf) {
+extern "C++" {
+int sr::gunzip_if_needed(const uint8_t *&p, size_t &n, std::vector<uint8_t> &buf) {
   if (n < 2 || p[0] != 0x1f || p[1] != 0x8b) return 0;
   z_stream z;
   memset(&z, 0, sizeof(z));
@@ -837,6 +838,7 @@ static int gunzip_if_needed(const uint8_t *&p, size_t &n, std::vector<uint8_t> &
   n = buf.size();
   return 0;
 }
+}  // extern "C++"
 
 int spring_reorder_load_fastq(spring_reorder_ctx *ctx, const uint8_t *fastq_1, size_t nbytes_1, const uint8_t *fastq_2,
                               size_t nbytes_2, spring_fastq_info *info) {
