@@ -159,6 +159,10 @@ def ref_units():
         U.ref_u_correct_order.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_char_p]
         U.ref_u_enc_bits3_roundtrip.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_void_p, C.c_char_p]
         U.ref_u_readsingletons.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(U, "ref_u_dec_noise"):   # a library built before these entry points existed stays usable
+            U.ref_u_dec_noise.argtypes = [C.c_void_p]
+            U.ref_u_enc_noise.argtypes = [C.c_void_p]
+            U.ref_u_unpack_seq.argtypes = [C.c_char_p, C.c_int, C.c_int]
         _UNITS = U
     return _UNITS
 
@@ -210,6 +214,175 @@ def ref_order(mode, order):
 def ref_bsc_bin():
     path = os.path.join(_HERE, "_ref", "ref_bsc")
     return path if os.path.exists(path) else None
+
+
+def ref_streams_bin():
+    """oracle/_ref/ref_streams: the real reorder_compress_streams + BSC_decompress behind a command line, or None."""
+    path = os.path.join(_HERE, "_ref", "ref_streams")
+    return path if os.path.exists(path) else None
+
+
+REF_STREAMS = ("read_flag.txt", "read_pos.bin", "read_noise.txt", "read_noisepos.bin", "read_rev.txt",
+               "read_unaligned.txt", "read_lengths.bin", "read_pos_pair.bin", "read_rev_pair.txt")
+
+
+def ref_streams(enc, num_reads, paired_end, preserve_order, num_reads_per_block, num_thr=1):
+    """Runs the REAL writer (reorder_compress_streams.cpp) on the encoder's streams `enc` (pos, rc, noise, noisepos,
+    order, rlen, unaligned) -> ({stream name: [raw bytes of block 0, 1, ...]}, sorted names of every file left)."""
+    import tempfile
+    na = len(enc["pos"])
+    ubases = int(np.asarray(enc["rlen"], np.uint64)[na:].sum())
+    with tempfile.TemporaryDirectory() as d:
+        for name, data in (("read_pos.bin", np.asarray(enc["pos"], np.uint64).tobytes()),
+                           ("read_rev.txt", bytes(enc["rc"])), ("read_noise.txt", bytes(enc["noise"])),
+                           ("read_noisepos.bin", np.asarray(enc["noisepos"], np.uint16).tobytes()),
+                           ("read_order.bin", np.asarray(enc["order"], np.uint32).tobytes()),
+                           ("read_lengths.bin", np.asarray(enc["rlen"], np.uint16).tobytes()),
+                           ("read_unaligned.txt", bytes(enc["unaligned"])),
+                           ("read_unaligned.txt.count", np.array([ubases], np.uint64).tobytes())):
+            with open(os.path.join(d, name), "wb") as f:
+                f.write(data)
+        subprocess.run([ref_streams_bin(), d, str(int(num_reads)), str(int(paired_end)), str(int(preserve_order)),
+                        str(int(num_reads_per_block)), str(int(num_thr))], check=True)
+        left = sorted(os.listdir(d))
+        blocks = {}
+        for s in REF_STREAMS:
+            b = 0
+            while os.path.exists(os.path.join(d, "%s.%d" % (s, b))):
+                with open(os.path.join(d, "%s.%d" % (s, b)), "rb") as f:
+                    blocks.setdefault(s, []).append(f.read())
+                b += 1
+        return blocks, left
+
+
+_QUALID = None
+
+
+def ref_qualid_lib():
+    """oracle/_ref/libref_qualid.so: the REAL reorder_compress_quality_id, BSC_str_array_decompress, id codec, binning
+    tables, quantize_quality and paired-id functions (util.cpp:113-267) behind a C ABI, or None."""
+    global _QUALID
+    if _QUALID is None:
+        path = os.path.join(_HERE, "_ref", "libref_qualid.so")
+        if not os.path.exists(path):
+            return None
+        Q = C.CDLL(path)
+        Q.ref_q_write.argtypes = [C.c_char_p, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int]
+        Q.ref_q_read_quality.restype = C.c_long
+        Q.ref_q_read_quality.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_long]
+        Q.ref_q_read_ids.restype = C.c_long
+        Q.ref_q_read_ids.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_long, C.c_void_p]
+        Q.ref_q_illumina_table.restype = None
+        Q.ref_q_illumina_table.argtypes = [C.c_void_p]
+        Q.ref_q_binary_table.restype = None
+        Q.ref_q_binary_table.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_uint]
+        Q.ref_q_quantize.restype = None
+        Q.ref_q_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        Q.ref_q_find_id_pattern.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t]
+        Q.ref_q_check_id_pattern.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int]
+        Q.ref_q_modify_id.restype = None
+        Q.ref_q_modify_id.argtypes = [C.c_void_p, C.c_size_t, C.c_int]
+        _QUALID = Q
+    return _QUALID
+
+
+def ref_quality_table(mode, thr=0, high=0, low=0):
+    """The real generate_illumina_binning_table ('illumina') / generate_binary_binning_table ('binary') -> 128 bytes."""
+    t = np.zeros(128, np.uint8)
+    if mode == "illumina":
+        ref_qualid_lib().ref_q_illumina_table(t.ctypes.data)
+    else:
+        ref_qualid_lib().ref_q_binary_table(t.ctypes.data, thr, high, low)
+    return t.tobytes()
+
+
+def ref_quantize(lines, table):
+    """The real quantize_quality on a list of byte lines -> the list after it."""
+    buf = np.frombuffer(b"".join(lines), np.uint8).copy()
+    off = np.concatenate([[0], np.cumsum([len(x) for x in lines])]).astype(np.uint64)
+    t = np.frombuffer(bytes(table), np.uint8).copy()
+    assert len(t) == 128
+    if len(buf):
+        ref_qualid_lib().ref_q_quantize(buf.ctypes.data, off.ctypes.data, len(lines), t.ctypes.data)
+    raw = buf.tobytes()
+    return [raw[int(off[i]):int(off[i + 1])] for i in range(len(lines))]
+
+
+def ref_find_id_pattern(a, b):
+    return ref_qualid_lib().ref_q_find_id_pattern(a, len(a), b, len(b))
+
+
+def ref_check_id_pattern(a, b, code):
+    r = ref_qualid_lib().ref_q_check_id_pattern(a, len(a), b, len(b), code)
+    assert r >= 0
+    return bool(r)
+
+
+def ref_modify_id(a, code):
+    buf = C.create_string_buffer(bytes(a), len(a))
+    ref_qualid_lib().ref_q_modify_id(buf, len(a), code)
+    return buf.raw
+
+
+def ref_read_ids(path, count):
+    """The real decompress_id_block on one block file -> list of ids."""
+    cap = 4096 * max(count, 1)
+    out = np.zeros(cap, np.uint8)
+    off = np.zeros(count + 1, np.uint64)
+    nb = ref_qualid_lib().ref_q_read_ids(path.encode(), count, out.ctypes.data, cap, off.ctypes.data)
+    assert nb >= 0, "decompress_id_block failed"
+    raw = out[:nb].tobytes()
+    return [raw[int(off[i]):int(off[i + 1])] for i in range(count)]
+
+
+def ref_read_quality(path, lens):
+    """The real BSC_str_array_decompress on one block file with the lines' lengths -> the lines back to back.
+    A block that holds more bytes than the lengths take makes the reference throw (AssertionError here); one that holds
+    fewer leaves NUL bytes at the end."""
+    lens = np.ascontiguousarray(lens, np.uint32)
+    cap = int(lens.sum()) + 16
+    out = np.zeros(cap, np.uint8)
+    nb = ref_qualid_lib().ref_q_read_quality(path.encode(), len(lens), lens.ctypes.data, out.ctypes.data, cap)
+    assert nb >= 0, "BSC_str_array_decompress failed"
+    return out[:nb].tobytes()
+
+
+def ref_qualid(files, order, num_reads, paired_end, num_reads_per_block, quality_lens, num_thr=1,
+               paired_id_match=False):
+    """Runs the REAL reorder_compress_quality_id (qvz off) on line images: files = {"quality_1": bytes, "id_1": ...,
+    "quality_2", "id_2"} (every line ends in '\n'), order = read_order.bin.  quality_lens[name] = the line lengths in
+    slot order that BSC_str_array_decompress needs (the decompressor takes them from read_lengths.bin).
+    -> ({name: [per block: bytes of the lines back to back (quality) / list of ids (id)]}, sorted names of files left)."""
+    import tempfile
+    Q = ref_qualid_lib()
+    U = num_reads // 2 if paired_end else num_reads
+    B = int(num_reads_per_block)
+    nb = (U + B - 1) // B
+    with tempfile.TemporaryDirectory() as d:
+        for name, data in files.items():
+            with open(os.path.join(d, name), "wb") as f:
+                f.write(data)
+        with open(os.path.join(d, "read_order.bin"), "wb") as f:
+            f.write(np.asarray(order, np.uint32).tobytes())
+        rc = Q.ref_q_write(d.encode(), num_reads, int(paired_end), B, num_thr,
+                           int(any(k.startswith("quality") for k in files)), int(any(k.startswith("id") for k in files)),
+                           int(paired_id_match))
+        assert rc == 0
+        left = sorted(os.listdir(d))
+        out = {}
+        for name in files:
+            if name == "id_2" and paired_id_match:
+                continue
+            blocks = []
+            for b in range(nb):
+                path = os.path.join(d, "%s.%d" % (name, b))
+                cnt = min(B, U - b * B)
+                if name.startswith("id"):
+                    blocks.append(ref_read_ids(path, cnt))
+                else:
+                    blocks.append(ref_read_quality(path, quality_lens[name][b * B:b * B + cnt]))
+            out[name] = blocks
+        return out, left
 
 
 def limbs(L):

@@ -1,15 +1,18 @@
 // oracle/ref_units_driver.cpp -- TEST INFRASTRUCTURE.
 //
 // C-ABI driver around the parts of the REAL reference main loop that compile in this image without Boost.
-// oracle/Makefile generates three translation units under oracle/_ref/gen/ (never committed) by LINE RANGE from
+// oracle/Makefile generates these translation units under oracle/_ref/gen/ (never committed) by LINE RANGE from
 // the sources where they lie under /root/reference/src -- nothing is edited, nothing is stood in for:
 //   reorder_units.gen.h   = reorder.h:33-318 (reorder_global, bitsettostring, setglobalarrays, updaterefcount,
 //                           readDnaFile, search_match) behind reorder.h's own non-Boost includes (:18-20, :24-36)
 //   encoder_units.gen.h   = encoder.h:34-122 (encoder_global_b, encoder_global, contig_reads, declarations,
 //                           bitsettostring) + :496-571 (setglobalarrays, readsingletons)
-//   util_units.gen.cpp    = util.cpp:31-54 (read_fastq_block), :269-394 (write/read_dna[N]_in/from_bits,
-//                           reverse_complement x2, remove_CR_from_end)
+//   util_units.gen.cpp    = util.cpp:31-54 (read_fastq_block), :113-267 (id block codec calls, quantize_quality,
+//                           binning tables, id patterns; used by ref_qualid_driver.cpp), :269-394
+//                           (write/read_dna[N]_in/from_bits, reverse_complement x2, remove_CR_from_end)
 //   encoder_units.gen.cpp = encoder.cpp:32-109 (buildcontig, writecontig), :177-222 (correct_order)
+//   decompress_units.gen.cpp = decompress.cpp:615-end (decompress_unpack_seq, set_dec_noise_array) behind the file's
+//                           own includes (:15-24); BSC_decompress comes from the real libbsc
 // What stays unbuildable: the reorder() driver loop (reorder.h:320-641: Boost gzip streams at :355-368),
 // writetofile (:643-730, Boost at :656-658), encode<>() (encoder.h:124-494, Boost at :153-176), preprocess().
 //
@@ -30,8 +33,15 @@
 #include <vector>
 #include <unistd.h>
 
+#include <omp.h>
+
 #include "reorder_units.gen.h"
 #include "encoder_units.gen.h"
+
+namespace spring {  // decompress.cpp:615-end, compiled by line range into decompress_units.gen.cpp
+void decompress_unpack_seq(const std::string &infile_seq, const int &num_thr_e, const int &num_thr);
+void set_dec_noise_array(char **dec_noise);
+}  // namespace spring
 
 namespace {
 
@@ -502,6 +512,36 @@ int ref_u_readsingletons(const char *dir, uint32_t numreads_s, uint32_t numreads
   spring::readsingletons<1536>(read, order_s, lens, eg, egb);
   for (uint32_t i = 0; i < m; i++) std::memcpy(limbs_out + (size_t)i * 24, (const void *)&read[i], 1536 / 8);
   delete[] read;
+  return 0;
+}
+
+// real set_dec_noise_array (decompress.cpp:664-685) -> table[128][128], untouched entries 0
+int ref_u_dec_noise(char *table) {
+  std::memset(table, 0, 128 * 128);
+  std::vector<char *> rows(128);
+  for (int i = 0; i < 128; i++) rows[i] = table + 128 * i;
+  spring::set_dec_noise_array(rows.data());
+  return 0;
+}
+
+// the enc_noise table of the real setglobalarrays (encoder.h:517-540) -> table[128][128], untouched entries 0
+int ref_u_enc_noise(char *table) {
+  spring::encoder_global eg;
+  spring::encoder_global_b<64> egb(1);
+  eg.max_readlen = 1;
+  std::memset(eg.enc_noise, 0, sizeof(eg.enc_noise));
+  spring::setglobalarrays<64>(eg, egb);
+  std::memcpy(table, eg.enc_noise, 128 * 128);
+  return 0;
+}
+
+// real decompress_unpack_seq (decompress.cpp:615-662): `<infile_seq>.<t>.bsc` + `<infile_seq>.<t>.tail` for
+// t < num_thr_e -> the consensus text of tid t in `<infile_seq>.<t>`
+int ref_u_unpack_seq(const char *infile_seq, int num_thr_e, int num_thr) {
+  omp_set_num_threads(num_thr);
+  try {
+    spring::decompress_unpack_seq(infile_seq, num_thr_e, num_thr);
+  } catch (std::exception &) { return -1; }
   return 0;
 }
 

@@ -1,0 +1,76 @@
+"""Writes tests/golden/ref_streams_<case>.npz and ref_qualid_<case>.npz: what the REFERENCE'S OWN writers produce for
+a handful of the hand-built cases of tests/ref_cases.py, so that the GPU tests can compare with reference-written
+blocks where oracle/_ref is not built.  Reads only oracle/_ref (ref_streams, libref_qualid.so; `make -C oracle`), never
+the reference tree.  Data only: the inputs and the raw blocks.  Run: python tests/golden/make_ref_golden.py
+
+ref_streams_<case>.npz   the encoder image (pos, rc, noise, noisepos, order, rlen, unaligned), the consensus `seq`, the
+                         original `reads` in slot order ('\n'-joined), num_reads / paired_end / preserve_order /
+                         num_reads_per_block, and per stream `<name>` = the raw blocks back to back as
+                         reorder_compress_streams wrote them (inflated by the real BSC_decompress), `<name>.off` = the
+                         block offsets.
+ref_qualid_<case>.npz    the line images quality_1 / id_1 (/ quality_2 / id_2), `order` (read_order.bin), and per file
+                         `<name>.bytes` / `.len` / `.off` = the lines of every block as reorder_compress_quality_id wrote
+                         them (read back by the real BSC_str_array_decompress / decompress_id_block; ids with their
+                         '\n'), the line lengths in slot order and the block offsets; `quality_<m>.illumina.*` = the
+                         same after the real quantize_quality with the real Illumina table, as preprocess applies it."""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+import ref_cases as rc  # noqa: E402
+import streams_model as sm  # noqa: E402
+from oracle import pyoracle as po  # noqa: E402
+
+assert po.ref_streams_bin() and po.ref_qualid_lib(), "oracle/_ref is not built"
+u8 = lambda b: np.frombuffer(bytes(b), np.uint8)  # noqa: E731
+offsets = lambda sizes: np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)  # noqa: E731
+
+for case in rc.STREAM_FIXTURES:
+    enc, seq, N, reads, pe, preserve_order, B = rc.stream_fixture_inputs(case)
+    blocks, left = po.ref_streams(enc, N, pe, preserve_order, B, num_thr=2)
+    out = {k: (u8(enc[k]) if isinstance(enc[k], bytes) else np.asarray(enc[k])) for k in rc.ENC_KEYS}
+    out.update(seq=u8(seq.encode()), reads=u8("\n".join(reads).encode()), num_reads=np.uint32(N), paired_end=np.bool_(pe),
+               preserve_order=np.bool_(preserve_order), num_reads_per_block=np.uint32(B))
+    for s in sm.stream_names(pe):
+        out[s] = u8(b"".join(blocks[s]))
+        out[s + ".off"] = offsets([len(x) for x in blocks[s]])
+    path = os.path.join(HERE, "ref_streams_%s.npz" % case)
+    np.savez_compressed(path, **out)
+    print(case, N, len(blocks["read_flag.txt"]), os.path.getsize(path))
+
+for case in rc.QUALID_FIXTURES:
+    files, order, n, pe, B = rc.qualid_fixture_inputs(case)
+    U = n // 2 if pe else n
+    out = dict(order=order, num_reads=np.uint32(n), paired_end=np.bool_(pe), num_reads_per_block=np.uint32(B))
+    slot = po.ref_order("pe" if pe else "se", order)   # the real generate_order_pe / _se: line j -> slot
+    for table in ("none", "illumina"):
+        f = dict(files)
+        if table == "illumina":
+            f = {k: po.ref_quantize(v, po.ref_quality_table("illumina")) for k, v in files.items() if k.startswith("quality")}
+        lens = {}
+        for k, v in f.items():
+            if k.startswith("quality"):
+                ln = np.zeros(U, np.uint32)
+                ln[slot] = [len(x) for x in v]
+                lens[k] = ln
+        got, left = po.ref_qualid({k: rc.image(v) for k, v in f.items()}, order, n, pe, B, lens, num_thr=2)
+        for k in f:
+            key = k + ("" if table == "none" else ".illumina")
+            if k.startswith("id"):
+                lines = [x for blk in got[k] for x in blk]
+                out[key + ".bytes"] = u8(b"".join(x + b"\n" for x in lines))
+                out[key + ".len"] = np.array([len(x) for x in lines], np.uint32)
+                out[key + ".off"] = offsets([sum(len(x) + 1 for x in blk) for blk in got[k]])
+            else:
+                out[key + ".bytes"] = u8(b"".join(got[k]))
+                out[key + ".len"] = lens[k]
+                out[key + ".off"] = offsets([len(x) for x in got[k]])
+    for k, v in files.items():
+        out[k] = u8(rc.image(v))
+    path = os.path.join(HERE, "ref_qualid_%s.npz" % case)
+    np.savez_compressed(path, **out)
+    print(case, n, os.path.getsize(path))

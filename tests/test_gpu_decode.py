@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import decode_cases as dc
+import ref_cases as rc
 import streams_model as sm
 from helpers import GOLDEN, interleave_order_N, make_N_reads, named_set, read_strings
 from oracle import pyoracle as po
@@ -88,6 +89,41 @@ def test_corner_cases(pe, preserve_order, B):
             assert info["num_units"] == (N // 2 if pe else N) and info["pos_escapes"] == ss.info["pos_escapes"]
             assert info["n_aligned"] + info["n_unaligned"] == N
     assert want is not None or (pe and not preserve_order and B == 3)
+
+
+# ---------------------------------------------------------------- 1b. blocks the reference's own writer wrote
+QUIRK = {"pe_corner_B3": 3, "pe_flags_B3": 0}   # case -> units that decode from the blocks before the first refused one
+
+
+@pytest.mark.parametrize("case", sorted(rc.STREAM_FIXTURES))
+def test_decodes_reference_written_blocks(case):
+    """The blocks the real reorder_compress_streams wrote (tests/golden/ref_streams_<case>.npz), with the case's
+    consensus, decode to the case's original reads: the decoder against the real WRITER, no reader model in between.
+    Where a block opens with an unaligned read 1 and holds an aligned one later, the real writer stores that position
+    as a u16 delta against 0 (reorder_compress_streams.cpp:312-328) and the real reader takes the block's first
+    position as a u64 (decompress.cpp:229-247): the decoder refuses such a block, as test_corner_cases says of the
+    model-written one, and decodes the blocks before it."""
+    from spring_amd import DecodeStage
+    from spring_amd.reorder import ReorderError
+    g = rc.load_stream_fixture(case)
+    N, pe, po_, B = g["N"], g["pe"], g["preserve_order"], g["B"]
+    U = N // 2 if pe else N
+    with DecodeStage() as ds:
+        ds.seq_from_host(*pack_seq(g["seq"], 3))
+        if case not in QUIRK:
+            info = ds.from_host(g["streams"], N, pe, po_, B)
+            assert decoded(ds, pe) == g["reads"]
+            assert info["num_units"] == U and info["n_aligned"] + info["n_unaligned"] == N
+            assert info["n_aligned"] == len(g["enc"]["pos"])
+            return
+        with pytest.raises(ReorderError, match="code -1"):
+            ds.from_host(g["streams"], N, pe, po_, B)
+        with pytest.raises(ReorderError, match="code -4"):
+            ds.download(0)
+        k = QUIRK[case] // B   # whole blocks before the refused one
+        if k:
+            ds.from_host(window(g["streams"], 0, k), N, pe, po_, B)
+            assert ds.reads(0) == g["reads"][:k * B] and ds.reads(1) == g["reads"][U:U + k * B]
 
 
 # ---------------------------------------------------------------- 2. encoder output

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import qualid_model as qm
+import ref_cases as rc
 from helpers import GOLDEN, interleave_order_N, make_N_reads, named_set, read_strings
 from oracle import pyoracle as po
 
@@ -172,6 +173,32 @@ def test_tables(table):
             same(qs, qm.ID, qm.from_fastq(f, qm.ID, slots, B), (table, B, "id"))   # ids never see the table
             assert info["bytes_changed"] == want["changed"]
             assert (want["changed"] > 0) == (table != "none")
+
+
+@pytest.mark.parametrize("case", sorted(rc.QUALID_FIXTURES))
+@pytest.mark.parametrize("table", ["none", "illumina"])
+def test_equals_reference_written_blocks(case, table):
+    """Bytes, line lengths and block table against what the reference's own reorder_compress_quality_id wrote
+    (tests/golden/ref_qualid_<case>.npz, recorded by tests/golden/make_ref_golden.py; the Illumina case by the real
+    quantize_quality before the real writer, as preprocess does), from both input forms: no model in between."""
+    from spring_amd import QualIdStage
+    g = rc.load_qualid_fixture(case)
+    t = QualIdStage.quality_table("illumina") if table == "illumina" else None
+    with QualIdStage() as qs:
+        qs.set_order(g["order"], g["N"], g["pe"])
+        for m in range(2 if g["pe"] else 1):
+            qname, iname = "quality_%d" % (m + 1), "id_%d" % (m + 1)
+            wq, wi = g["want"][(qname, table)], g["want"][(iname, "none")]
+            quals, ids = g["files"][qname].split(b"\n")[:-1], g["files"][iname].split(b"\n")[:-1]
+            fastq = b"".join(b"%s\n%s\n+\n%s\n" % (i, b"A" * len(q), q) for i, q in zip(ids, quals))
+            info = qs.from_fastq(fastq, table=t, num_reads_per_block=g["B"])
+            same(qs, qm.QUALITY, wq, (case, table, m, "fastq"))
+            same(qs, qm.ID, wi, (case, table, m, "fastq id"))
+            assert (info["bytes_changed"] > 0) == (table == "illumina")
+            qs.from_lines(qm.QUALITY, g["files"][qname], table=t, num_reads_per_block=g["B"])
+            same(qs, qm.QUALITY, wq, (case, table, m, "lines"))
+            qs.from_lines(qm.ID, g["files"][iname], table=t, num_reads_per_block=g["B"])
+            same(qs, qm.ID, wi, (case, table, m, "lines id"))
 
 
 @pytest.mark.parametrize("pe", [False, True])

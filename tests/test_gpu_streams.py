@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import ref_cases as rc
 import streams_model as sm
 from helpers import interleave_order_N, make_N_reads, named_set, read_strings
 from oracle import pyoracle as po
@@ -77,6 +78,22 @@ def test_gpu_corner_cases_from_host(pe, preserve_order, B):
         _same(ss, want, (pe, preserve_order, B))
         if not preserve_order and pe and B == 3:
             assert info["pos_escapes"] == 2 and info["flag_count"] == [3, 2, 1, 1, 1]
+
+
+@pytest.mark.parametrize("case", sorted(rc.STREAM_FIXTURES))
+def test_gpu_equals_reference_written_blocks(case):
+    """Every stream and block table against what the reference's own reorder_compress_streams wrote for the case
+    (tests/golden/ref_streams_<case>.npz, recorded by tests/golden/make_ref_golden.py): no model in between."""
+    from spring_amd.streams import StreamsStage
+    g = rc.load_stream_fixture(case)
+    enc = g["enc"]
+    with StreamsStage() as ss:
+        info = ss.from_host(enc["pos"], enc["rc"], enc["noise"], enc["noisepos"], enc["order"], enc["rlen"],
+                            enc["unaligned"], g["N"], g["pe"], g["preserve_order"], g["B"])
+        _same(ss, g["streams"], case)
+        flags = np.frombuffer(g["streams"]["read_flag.txt"][0], np.uint8) - ord("0")
+        assert np.array_equal(np.bincount(flags, minlength=5), info["flag_count"])
+        assert info["num_blocks"] == ((g["N"] // 2 if g["pe"] else g["N"]) + g["B"] - 1) // g["B"]
 
 
 def test_gpu_refuses_bad_input():
