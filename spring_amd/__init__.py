@@ -8,3 +8,4 @@ from .reorder import (CompressionParams, ReorderError, ReorderOpts, ReorderStage
 from .streams import StreamsStage, call_reorder_compress_streams  # noqa: F401,E402
 from .decode import DecodeStage  # noqa: F401,E402
 from .qualid import QualIdStage  # noqa: F401,E402
+from .fastq_out import FastqOutStage  # noqa: F401,E402

@@ -45,6 +45,12 @@ QUALID_EXPORTS = [
     "spring_quality_table", "spring_id_pattern",
 ]
 
+# include/spring_fastq_out.h: a list of its own as well
+FASTQ_OUT_EXPORTS = [
+    "spring_fastq_out_create", "spring_fastq_out_destroy", "spring_fastq_out_assemble", "spring_fastq_out_download",
+    "spring_fastq_out_write", "spring_fastq_out_get_info",
+]
+
 
 class Opts(C.Structure):
     _fields_ = [("device", C.c_int32), ("num_chains", C.c_uint32), ("num_thr", C.c_int32),
@@ -102,6 +108,27 @@ class QualIdInfo(C.Structure):
             v = getattr(self, k)
             d[k] = list(v) if hasattr(v, "__len__") else v
         return d
+
+
+class FastqOutParams(C.Structure):
+    _fields_ = ([(k, C.c_uint32) for k in ("first_block", "num_blocks", "num_reads", "num_reads_per_block")]
+                + [(k, C.c_int32) for k in ("paired_end", "mate", "preserve_quality", "id_mode", "paired_id_code", "pad")]
+                + [("range_start", C.c_uint64), ("range_end", C.c_uint64)])
+
+
+class FastqOutSources(C.Structure):
+    _fields_ = [("decode", C.c_void_p), ("bases", C.c_void_p), ("read_off", C.c_void_p),
+                ("quality_ctx", C.c_void_p), ("quality", C.c_void_p), ("quality_bytes", C.c_uint64),
+                ("quality_block_off", C.c_void_p),
+                ("id_ctx", C.c_void_p), ("ids", C.c_void_p), ("id_bytes", C.c_uint64), ("id_block_off", C.c_void_p)]
+
+
+class FastqOutInfo(C.Structure):
+    _fields_ = [("num_units", C.c_uint64), ("first_slot", C.c_uint64), ("bytes", C.c_uint64),
+                ("ms_device", C.c_double), ("ms_file", C.c_double)]
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class DecodeInfo(C.Structure):
@@ -257,6 +284,17 @@ def lib():
     L.spring_quality_table.argtypes = [C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, u8p]
     L.spring_id_pattern.argtypes = [u8p, C.c_size_t, u8p, C.c_size_t, C.c_int32, C.POINTER(C.c_uint8),
                                     C.POINTER(C.c_double)]
+    L.spring_fastq_out_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.spring_fastq_out_destroy.argtypes = [vp]
+    L.spring_fastq_out_destroy.restype = None
+    L.spring_fastq_out_assemble.argtypes = [vp, C.POINTER(FastqOutParams), C.POINTER(FastqOutSources),
+                                            C.POINTER(FastqOutInfo)]
+    L.spring_fastq_out_download.argtypes = [vp, u8p, vp]
+    L.spring_fastq_out_write.argtypes = [vp, C.c_char_p, C.c_int32, C.POINTER(FastqOutInfo)]
+    L.spring_fastq_out_get_info.argtypes = [vp, C.POINTER(FastqOutInfo)]
+    for name in FASTQ_OUT_EXPORTS:
+        if name != "spring_fastq_out_destroy":
+            getattr(L, name).restype = C.c_int
     for name in QUALID_EXPORTS:
         if name != "spring_qualid_destroy":
             getattr(L, name).restype = C.c_int

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "encoder_internal.h"
+#include "fastq_out_internal.h"
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_decode.h"
@@ -768,6 +769,18 @@ int spring_decode_get_info(spring_decode_ctx *ctx, spring_decode_info *info) {
 }
 
 }  // extern "C"
+
+namespace sr {
+int decode_view(spring_decode_ctx *ctx, DecodeView *v) {
+  if (!ctx || !v) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  if (!ctx->have) return fail(SPRING_REORDER_E_STATE, "nothing decoded yet");
+  v->dev = ctx->dev;
+  v->info = ctx->info;
+  v->paired_end = ctx->off[1].p != nullptr;
+  for (int m = 0; m < 2; m++) { v->bases[m] = ctx->out[m].as<uint8_t>(); v->read_off[m] = ctx->off[m].as<uint64_t>(); }
+  return 0;
+}
+}  // namespace sr
 
 // ------------------------------------------------------------------ file contract
 namespace {

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "encoder_internal.h"
+#include "fastq_out_internal.h"
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_qualid.h"
@@ -351,6 +352,7 @@ struct spring_qualid_ctx {
   bool have = false;       // a result of the last from_* call exists
   bool have_kind[2] = {false, false};
   spring_qualid_info info;
+  uint32_t B = 0;          // num_reads_per_block of the result
   DBuf out[2], len[2];
   std::vector<uint64_t> table[2];   // num_blocks + 1 block offsets
 };
@@ -511,6 +513,7 @@ int run_core(spring_qualid_ctx *ctx, const uint8_t *text, size_t nbytes, bool fa
   info.max_len[0] = mx[0]; info.max_len[1] = mx[1];
   info.ms_device = ms;
   ctx->info = info;
+  ctx->B = B;
   for (int k = 0; k < 2; k++) ctx->have_kind[k] = (want >> k & 1) != 0;
   ctx->have = true;
   if (info_out) *info_out = info;
@@ -725,3 +728,19 @@ int spring_id_pattern(const uint8_t *fastq_1, size_t nbytes_1, const uint8_t *fa
 }
 
 }  // extern "C"
+
+namespace sr {
+int qualid_view(spring_qualid_ctx *ctx, QualIdView *v) {
+  if (!ctx || !v) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  if (!ctx->have) return fail(SPRING_REORDER_E_STATE, "no quality / id blocks computed yet");
+  v->dev = ctx->dev;
+  v->info = ctx->info;
+  v->num_reads_per_block = ctx->B;
+  for (int k = 0; k < 2; k++) {
+    v->have[k] = ctx->have_kind[k];
+    v->bytes[k] = ctx->out[k].as<uint8_t>();
+    v->table[k] = ctx->table[k].data();
+  }
+  return 0;
+}
+}  // namespace sr
