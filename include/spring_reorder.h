@@ -99,6 +99,11 @@ typedef struct {
                              re-orders the runs where two keys share them (same result as the full sort).  0 = the library's
                              choice, 64 = the full 64-bit sort, small values force the repair and its
                              fall-back (tests).  Anything outside 0 .. 64 is refused by spring_reorder_create */
+  int32_t dict_build_mode;  /* dictionary build, same results either way.  0 = the library's choice: pools of one read length get
+                             their dictionary keys from the unpack pass, and the hash-addressed table is written in one pass,
+                             front to back.  1 = a key pass over the unpacked reads, a memset of the
+                             table, the merged list of both dictionaries and the insert pass over it.  stats.dict_build_path
+                             says what ran.  Anything else is refused by spring_reorder_create */
 } spring_reorder_opts;
 
 typedef struct {
@@ -132,6 +137,8 @@ typedef struct {
   uint64_t sort_full_sorts;    /* ... dictionaries that were sorted again over all 64 bits (run too long, or too many runs) */
   uint64_t sort_long_runs;     /* ... of those: because a run holding several keys was longer than the repair takes (1 024 entries) */
   uint64_t sort_list_overflows;/* ... of those: because more hash changes inside runs were found than the repair's list holds */
+  uint64_t dict_build_path;    /* last dictionary build: bit 0 = the keys came from the unpack pass (clear: a key pass over the
+                                  reads), bit 1 = the table was written in one pass (clear: memset, merge and insert passes) */
 } spring_reorder_stats;
 
 void spring_reorder_default_opts(spring_reorder_opts *o);

@@ -29,6 +29,7 @@
 #include <zlib.h>
 
 #include "reorder_device.h"
+#include "dict_build.h"
 #include "reorder_internal.h"
 #include "spring_reorder.h"
 #include "synth_common.h"
@@ -138,6 +139,10 @@ struct spring_reorder_ctx {
   bool uniform = true;
   uint64_t *d_reads = nullptr;
   uint16_t *d_lens = nullptr;
+  // (mix64(window), id) pairs of both dictionaries, written by the unpack pass (k_unpack_fixed_keys) for the next
+  // build_dict, which takes them over; null: build_dict runs its key pass
+  uint64_t *pre_keys[2] = {nullptr, nullptr};
+  uint32_t *pre_vals[2] = {nullptr, nullptr};
   DictDev dict[2];
   uint4 *fpt = nullptr;   // one bucket table for both dictionaries (reorder_kernels.hip, tab_find): nb buckets of 32 bytes
   int bshift = 63;        // plain home bucket = hash >> bshift (nb = 2^(64 - bshift) buckets)
@@ -368,6 +373,8 @@ int spring_reorder_create(spring_reorder_ctx **out, const spring_reorder_opts *o
   if (o.num_thr <= 0) return fail(SPRING_REORDER_E_ARG, "num_thr must be >= 1");
   if (o.sort_prefix_bits < 0 || o.sort_prefix_bits > 64)
     return fail(SPRING_REORDER_E_ARG, "sort_prefix_bits: 0 (library's choice) or 1 .. 64 bits of the key hash (64 = the full sort)");
+  if (o.dict_build_mode < 0 || o.dict_build_mode > 1)
+    return fail(SPRING_REORDER_E_ARG, "dict_build_mode: 0 (library's choice) or 1 (key pass, memset, merge and insert passes)");
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (ndev <= 0) return fail(SPRING_REORDER_E_HIP, "no HIP device");
@@ -420,12 +427,37 @@ static int setup_geometry(spring_reorder_ctx *ctx, uint32_t n, uint32_t max_read
   return 0;
 }
 
-static int unpack_on_device(spring_reorder_ctx *ctx, uint32_t *d_bad_len = nullptr) {
+static void drop_pre_keys(spring_reorder_ctx *ctx) {
+  for (int l = 0; l < 2; l++) {
+    ctx->dfree(ctx->pre_keys[l]); ctx->pre_keys[l] = nullptr;
+    ctx->dfree(ctx->pre_vals[l]); ctx->pre_vals[l] = nullptr;
+  }
+}
+
+// with_keys: a stream of fixed-size records of one read length -- every read is in both dictionaries and the window
+// parameters are known now, so the unpack pass also writes the pairs build_dict would otherwise make in a pass of its own
+static int unpack_on_device(spring_reorder_ctx *ctx, uint32_t *d_bad_len = nullptr, bool with_keys = false) {
   if (!ctx->d_reads) DMALLOC(ctx->d_reads, (size_t)std::max<uint32_t>(ctx->n, 1) * ctx->S * sizeof(uint64_t));
   if (!ctx->d_lens) DMALLOC(ctx->d_lens, (size_t)std::max<uint32_t>(ctx->n, 1) * sizeof(uint16_t));
-  HIPCHK(hipEventRecord(ctx->ev[0], ctx->st));
+  drop_pre_keys(ctx);
   const uint32_t rec = 2u + ((uint32_t)ctx->L + 3u) / 4u;
-  launch_unpack(ctx->st, ctx->d_dna, ctx->d_off, ctx->n, ctx->L, ctx->W, ctx->S, rec, ctx->d_reads, ctx->d_lens, d_bad_len);
+  with_keys = with_keys && ctx->n && !ctx->d_off && ctx->uniform && ctx->o.dict_build_mode != 1 &&
+              ctx->L > ctx->dict[0].end && ctx->L > ctx->dict[1].end && ctx->dict[0].start >= 0;
+  if (with_keys) {
+    for (int l = 0; l < 2; l++) {
+      DMALLOC(ctx->pre_keys[l], (size_t)ctx->n * 8);
+      DMALLOC(ctx->pre_vals[l], (size_t)ctx->n * 4);
+    }
+  }
+  HIPCHK(hipEventRecord(ctx->ev[0], ctx->st));
+  if (with_keys && !launch_unpack_keys(ctx->st, ctx->d_dna, ctx->n, ctx->L, ctx->W, ctx->S, rec, ctx->d_reads, ctx->d_lens, d_bad_len,
+                                       ctx->dict[0].start, ctx->dict[0].end, ctx->dict[1].start, ctx->dict[1].end,
+                                       ctx->pre_keys[0], ctx->pre_vals[0], ctx->pre_keys[1], ctx->pre_vals[1])) {
+    with_keys = false;
+    drop_pre_keys(ctx);
+  }
+  if (!with_keys)
+    launch_unpack(ctx->st, ctx->d_dna, ctx->d_off, ctx->n, ctx->L, ctx->W, ctx->S, rec, ctx->d_reads, ctx->d_lens, d_bad_len);
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->st));
   ctx->stage = ST_LOADED;
@@ -561,12 +593,13 @@ int load_dna_source(spring_reorder_ctx *ctx, const DnaSource &src, uint32_t n, u
     uint32_t *d_bad = nullptr, bad = 0;
     DMALLOC(d_bad, 16);
     HIPCHK(hipMemsetAsync(d_bad, 0, 4, ctx->st));
-    if ((r = unpack_on_device(ctx, d_bad))) return r;
+    if ((r = unpack_on_device(ctx, d_bad, true))) return r;
     HIPCHK(hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, ctx->st));
     HIPCHK(hipStreamSynchronize(ctx->st));
     ctx->dfree(d_bad);
     if (!bad) return 0;
     ctx->stage = ST_CREATED;  // same size, other lengths: walk the records after all
+    drop_pre_keys(ctx);
     ctx->dfree(ctx->d_dna); ctx->d_dna = nullptr;
   }
   // variable-length (or malformed) stream: the record starts are sequentially dependent -> a host image is walked
@@ -657,7 +690,7 @@ int spring_reorder_load_dna(spring_reorder_ctx *ctx, const uint8_t *dna, size_t 
     DMALLOC(ctx->d_off, (size_t)n * sizeof(uint64_t));
     if ((r = upload_chunked(ctx, (uint8_t *)ctx->d_off, (size_t)n * sizeof(uint64_t), mem_fill, off.data()))) return r;
   }
-  return unpack_on_device(ctx);
+  return unpack_on_device(ctx, nullptr, true);
 }
 
 int spring_reorder_load_dna_device(spring_reorder_ctx *ctx, const void *d_dna, size_t nbytes, uint32_t n,
@@ -674,7 +707,7 @@ int spring_reorder_load_dna_device(spring_reorder_ctx *ctx, const void *d_dna, s
     ctx->d_dna = (uint8_t *)d_dna;
     ctx->dna_borrowed = true;
     ctx->dna_bytes = nbytes;
-    return unpack_on_device(ctx);
+    return unpack_on_device(ctx, nullptr, true);
   }
   // variable length: record starts are sequentially dependent -> walk a host copy
   std::vector<uint8_t> h(nbytes);
@@ -993,7 +1026,7 @@ int spring_reorder_load_synth(spring_reorder_ctx *ctx, uint32_t n, uint32_t L, u
   DMALLOC(ctx->d_dna, ctx->dna_bytes + 16);
   launch_synth(ctx->st, ctx->d_dna, n, L, G, seed, syn_err_thr24(err_ppm));
   HIPCHK(hipGetLastError());
-  return unpack_on_device(ctx);
+  return unpack_on_device(ctx, nullptr, true);
 }
 
 int spring_reorder_download_dna(spring_reorder_ctx *ctx, uint8_t *dst, size_t cap) {
@@ -1059,6 +1092,16 @@ int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
   const bool both_dense = n && ctx->uniform && ctx->L > ctx->dict[0].end && ctx->L > ctx->dict[1].end;
   uint64_t *keys_both[2] = {nullptr, nullptr};
   uint32_t *vals_both[2] = {nullptr, nullptr};
+  ctx->stats.dict_build_path = 0;
+  if (both_dense && ctx->pre_keys[0] && ctx->o.dict_build_mode != 1) {  // the unpack pass has written the pairs: no key pass
+    for (int l = 0; l < 2; l++) {
+      keys_both[l] = ctx->pre_keys[l]; vals_both[l] = ctx->pre_vals[l];
+      ctx->pre_keys[l] = nullptr; ctx->pre_vals[l] = nullptr;
+    }
+    ctx->stats.dict_build_path |= 1;
+  } else {
+    drop_pre_keys(ctx);
+  }
   ctx->stats.sort_repaired_runs = 0; ctx->stats.sort_full_sorts = 0; ctx->stats.sort_prefix_bits = 0;
   ctx->stats.sort_long_runs = 0; ctx->stats.sort_list_overflows = 0;
   for (int l = 0; l < 2; l++) {
@@ -1106,7 +1149,7 @@ int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
     DMALLOC(k_out, (size_t)m * 8);
     DMALLOC(d.ids, (size_t)m * 4);
     DBG_T("alloc keys");
-    if (l == 0 && both_dense) {  // one pass over the reads emits the pairs of both dictionaries
+    if (l == 0 && both_dense && !keys_both[0]) {  // one pass over the reads emits the pairs of both dictionaries
       DMALLOC(keys_both[1], (size_t)n * 8);
       DMALLOC(vals_both[1], (size_t)n * 4);
       launch_keys2(st, ctx->d_reads, n, ctx->S, d.start, d.end, ctx->dict[1].start, ctx->dict[1].end, k_in, v_in,
@@ -1213,10 +1256,54 @@ int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
   if (ctx->lshift < 1) return fail(SPRING_REORDER_E_ARG, "build_dict: table too large for minimizer addressing");
   ctx->stats.table_minz = ctx->minz; ctx->stats.table_marked_lines = 0;
   DMALLOC(ctx->fpt, nb * 32);
-  HIPCHK(hipMemsetAsync(ctx->fpt, 0, nb * 32, st));
+  // The hash-addressed table is written front to back, every bucket once, by k_tab_write (dict_build.hip): no memset --
+  // the pool hands back memory that held an earlier table -- and no merged list of the two dictionaries.
+  // opts.dict_build_mode = 1, the minimizer-addressed table and a pool without keys: memset + merge + insert passes.
+  const bool one_pass = nm && !ctx->minz && ctx->o.dict_build_mode != 1;
+  if (!one_pass) HIPCHK(hipMemsetAsync(ctx->fpt, 0, nb * 32, st));
   uint32_t *const tab_words = reinterpret_cast<uint32_t *>(ctx->fpt);
   DBG_T("alloc+memset tab");
-  if (nm) {
+  if (one_pass) {
+    if (nm >= 0xffffffffull) return fail(SPRING_REORDER_E_ARG, "build_dict: %llu keys exceed the 32-bit index space of the table build", (unsigned long long)nm);
+    ctx->stats.dict_build_path |= 2;
+    ctx->marked_lines = 0;
+    DictBuild db[2];
+    for (int l = 0; l < 2; l++) {
+      DictDev &d = ctx->dict[l];
+      db[l].ustart = ustart[l]; db[l].ucount = ucount[l]; db[l].ids = d.ids; db[l].urec = d.urec;
+      db[l].deep = d.deep; db[l].ndeep = d.d_ndeep;
+    }
+    uint32_t *d_part = nullptr, *d_ovf = nullptr, *d_ovf_blk = nullptr, *d_ovf_cnt = nullptr, novf = 0;
+    const size_t nblk = tab_write_blocks(ctx->bshift);
+    DMALLOC(d_part, 2 * (nblk + 1) * 4);
+    DMALLOC(d_ovf_blk, nblk * TAB_OVF_SLOTS * 4);
+    DMALLOC(d_ovf_cnt, nblk * 4);
+    DMALLOC(d_ovf, ((size_t)nm + 1) * 4);  // list of the overflow pairs a workgroup's own slots do not hold: room for every pair
+    HIPCHK(hipMemsetAsync(d_ovf, 0, 4, st));
+    launch_tab_partition(st, uhash[0], (uint32_t)nk0, uhash[1], (uint32_t)nk1, ctx->bshift, d_part);
+    launch_tab_write(st, uhash[0], (uint32_t)nk0, uhash[1], (uint32_t)nk1, d_part, db[0], db[1], ctx->fpt, ctx->bshift, d_ovf,
+                     d_ovf_blk, d_ovf_cnt);
+    launch_tab_overflow_blocks(st, uhash[0], (uint32_t)nk0, uhash[1], db[0], db[1], tab_words, ctx->bshift, d_ovf_blk, d_ovf_cnt);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&novf, d_ovf, 4, hipMemcpyDeviceToHost, st));
+    uint32_t nd[2][3] = {{0, 0, 0}, {0, 0, 0}};
+    for (int l = 0; l < 2; l++)
+      HIPCHK(hipMemcpyAsync(nd[l], ctx->dict[l].d_ndeep, 12, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    DBG_T("table write");
+    launch_tab_overflow_pairs(st, uhash[0], (uint32_t)nk0, uhash[1], db[0], db[1], tab_words, ctx->bshift, d_ovf, novf);
+    HIPCHK(hipGetLastError());
+    for (int l = 0; l < 2; l++) { ctx->dict[l].ndeep = nd[l][0]; ctx->dict[l].big_reads = nd[l][1]; ctx->dict[l].mid_reads = nd[l][2]; }
+    if (dbg) {
+      fprintf(stderr, "[dict] %u of %llu pairs past the %u overflow slots of their workgroup\n", novf, (unsigned long long)nm, TAB_OVF_SLOTS);
+      fprintf(stderr, "[dict] reads %u + %u, keys %u + %u, bins >= %u: %u + %u, reads in bins >= %u: %u + %u, >= %u: %u + %u\n",
+              ctx->dict[0].numreads, ctx->dict[1].numreads, ctx->dict[0].numkeys, ctx->dict[1].numkeys, DEEP_BIN, nd[0][0], nd[1][0],
+              MID_BIN, nd[0][2], nd[1][2], BIG_BIN, nd[0][1], nd[1][1]);
+    }
+    ctx->stats.table_marked_lines = 0;
+    ctx->dfree(d_part); ctx->dfree(d_ovf); ctx->dfree(d_ovf_blk); ctx->dfree(d_ovf_cnt);  // (dfree waits for the stream: the overflow pass has run)
+    DBG_T("overflow");
+  } else if (nm) {
     uint64_t *mv0 = nullptr, *mh = nullptr, *mv = nullptr;
     void *d_tmp = nullptr;
     const uint64_t *h_in = nullptr, *v_in = nullptr;

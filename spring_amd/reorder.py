@@ -54,6 +54,7 @@ class ReorderOpts:
     phases: int = 0           # chain schedule: 1 lock-step rounds, 2 two chain groups whose rounds alternate (the output depends on it), 0 = library's choice
     known_absent: int = 0     # four-chain round kernel: chains remember known-absent windows (0 on, -1 off; same results)
     sort_prefix_bits: int = 0  # dictionary sort: bits of the key hash the radix sort orders, the rest by exact repair (0 = library's choice, 64 = full sort; same results)
+    dict_build_mode: int = 0  # dictionary build: 0 = library's choice (keys from the unpack pass, table written in one pass), 1 = key pass + memset + merge + insert (same results)
 
     def to_c(self):
         o = _lib.Opts()
@@ -79,6 +80,7 @@ class ReorderOpts:
         o.phases = self.phases
         o.known_absent = self.known_absent
         o.sort_prefix_bits = self.sort_prefix_bits
+        o.dict_build_mode = self.dict_build_mode
         o.num_devices = len(self.devices)
         for i, d in enumerate(self.devices):
             o.devices[i] = d
