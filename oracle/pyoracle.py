@@ -255,6 +255,65 @@ def ref_streams(enc, num_reads, paired_end, preserve_order, num_reads_per_block,
         return blocks, left
 
 
+def ref_reorder_bin():
+    """oracle/_ref/ref_reorder: the real reorder_main<N> (reorder()'s loop, writetofile) behind a command line, or None."""
+    path = os.path.join(_HERE, "_ref", "ref_reorder")
+    return path if os.path.exists(path) else None
+
+
+def ref_encoder_bin():
+    """oracle/_ref/ref_encoder: the real encoder_main<N> (encode<>(), encoder.cpp whole) + BSC_decompress, or None."""
+    path = os.path.join(_HERE, "_ref", "ref_encoder")
+    return path if os.path.exists(path) else None
+
+
+def _run_ref_stage(argv, files, num_thr):
+    """Writes `files` into a temporary directory, runs argv[0] <dir> argv[1:] as a child process with OMP_NUM_THREADS set
+    for the child only -> ({file name: bytes} of everything left, sorted names, the child's stdout)."""
+    import tempfile
+    env = dict(os.environ, OMP_NUM_THREADS=str(int(num_thr)))
+    with tempfile.TemporaryDirectory() as d:
+        for name, data in files.items():
+            with open(os.path.join(d, name), "wb") as f:
+                f.write(data)
+        p = subprocess.run([argv[0], d] + [str(a) for a in argv[1:]], check=True, env=env, stdout=subprocess.PIPE)
+        left = sorted(os.listdir(d))
+        out = {}
+        for name in left:
+            with open(os.path.join(d, name), "rb") as f:
+                out[name] = f.read()
+        return out, left, p.stdout.decode()
+
+
+def _printed(text, tail):
+    """The number the stage printed in front of `tail` ("<n> singleton reads were aligned")."""
+    import re
+    m = re.search(r"(\d+)" + re.escape(tail), text)
+    assert m, (tail, text)
+    return int(m.group(1))
+
+
+def ref_reorder(dna1, dna2, L, n1, n2):
+    """Runs the REAL reorder_main<N> at one thread on input_clean_1.dna (+ input_clean_2.dna when dna2 is given).  The
+    gzip filter is the one thing left out (oracle/Makefile): read_rev.txt.0, tempflag.txt.0, temppos.txt.0 and
+    read_lengths.bin.0 come back uncompressed.  -> ({file name: bytes}, sorted names of every file left, the printed
+    number of unmatched reads)."""
+    files = {"input_clean_1.dna": dna1}
+    if dna2 is not None:
+        files["input_clean_2.dna"] = dna2
+    out, left, text = _run_ref_stage([ref_reorder_bin(), int(L), int(n1), int(n2)], files, 1)
+    return out, left, _printed(text, " were unmatched")
+
+
+def ref_encoder(files, L, T, num_reads, n_clean):
+    """Runs the REAL encoder_main<N> with T threads on the reorder stage's file set `files` ({name: bytes}, the four
+    gzip files of the reference uncompressed; input_N.dna and read_order_N.bin among them).  read_seq.bin.<t>.bsc is
+    inflated by the real BSC_decompress into read_seq.bin.<t>.raw.  -> ({file name: bytes}, sorted names of every file
+    left, (printed "singleton reads were aligned", printed "reads with N were aligned"))."""
+    out, left, text = _run_ref_stage([ref_encoder_bin(), int(L), int(T), int(num_reads), int(n_clean)], files, T)
+    return out, left, (_printed(text, " singleton reads were aligned"), _printed(text, " reads with N were aligned"))
+
+
 _QUALID = None
 
 

@@ -12,7 +12,14 @@ ref_qualid_<case>.npz    the line images quality_1 / id_1 (/ quality_2 / id_2), 
                          `<name>.bytes` / `.len` / `.off` = the lines of every block as reorder_compress_quality_id wrote
                          them (read back by the real BSC_str_array_decompress / decompress_id_block; ids with their
                          '\n'), the line lengths in slot order and the block offsets; `quality_<m>.illumina.*` = the
-                         same after the real quantize_quality with the real Illumina table, as preprocess applies it."""
+                         same after the real quantize_quality with the real Illumina table, as preprocess applies it.
+ref_stage_<case>.npz     the cases of tests/ref_stage_cases.py through the reference's whole stages (ref_reorder,
+                         ref_encoder): `in.dna` / `in.dnaN` / `in.order_N` (input_clean_1.dna, input_N.dna,
+                         read_order_N.bin), n, L, T, K, `reorder/<file>` = every file reorder_main<N> left (its four gzip
+                         files uncompressed; for thr3 the hand-made three-thread set instead, `reorder_by_reference` =
+                         False), `unmatched` = the number it printed, `encoder/<file>` = every file encoder_main<N> left
+                         on that set (read_seq.bin.<t>.raw = the .bsc inflated by the real BSC_decompress), `matched` =
+                         the two numbers it printed."""
 import os
 import sys
 
@@ -25,7 +32,9 @@ import ref_cases as rc  # noqa: E402
 import streams_model as sm  # noqa: E402
 from oracle import pyoracle as po  # noqa: E402
 
-assert po.ref_streams_bin() and po.ref_qualid_lib(), "oracle/_ref is not built"
+import ref_stage_cases as sc  # noqa: E402
+
+assert po.ref_streams_bin() and po.ref_qualid_lib() and po.ref_reorder_bin() and po.ref_encoder_bin(), "oracle/_ref is not built"
 u8 = lambda b: np.frombuffer(bytes(b), np.uint8)  # noqa: E731
 offsets = lambda sizes: np.concatenate([[0], np.cumsum(sizes)]).astype(np.uint64)  # noqa: E731
 
@@ -74,3 +83,11 @@ for case in rc.QUALID_FIXTURES:
     path = os.path.join(HERE, "ref_qualid_%s.npz" % case)
     np.savez_compressed(path, **out)
     print(case, n, os.path.getsize(path))
+
+LARGEST = 28763   # enc_var2k.npz, the largest fixture before these: none of the ref_stage files may be larger
+for case in sc.FIXTURES:
+    out = sc.record_fixture(case)
+    path = os.path.join(HERE, "ref_stage_%s.npz" % case)
+    np.savez_compressed(path, **out)
+    print(case, int(out["n"]), os.path.getsize(path))
+    assert os.path.getsize(path) <= LARGEST, case

@@ -104,6 +104,76 @@ SMALL_SETS = ["test_1", "test_1+2", "syn2k_100", "syn5k_150", "syn3k_64", "syn2k
               "heavy", "repeat10k", "dups", "tandem", "one", "two_same", "empty"]
 
 
+def early_stop_set():
+    """40 k reads of a small genome (25x) in the middle of 525 k unrelated random reads.  Chain 0 starts at read 0
+    (unrelated) and new seeds come from the top of the pool, so 520 k unrelated reads -- two failed searches each --
+    are consumed first: at iteration 1 000 000 more than half of the last million were unmatched and the search
+    stops (reorder.h:433-439) before the related reads are reached."""
+    L = 100
+    rng = np.random.default_rng(2024)
+    rel = rs.np_reads(5, 40_000 * L // 25, 40_000, L, 0.01)
+    unrel = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, (525_000, L))]
+    a = np.concatenate([unrel[:5000], rel, unrel[5000:]]).astype(np.uint8)
+    return rs.pack_fixed(a), a.shape[0], L, rs.pack_fixed(rel)
+
+
+# ------------------------------------------------------------------ file sets of the two stages (reorder.h:733-745, encoder.h:580-593)
+
+REORDER_TID_FILES = ("read_order.bin", "read_rev.txt", "tempflag.txt", "temppos.txt", "read_lengths.bin", "temp.dna")
+GZIP_TID_FILES = ("read_rev.txt", "tempflag.txt", "temppos.txt", "read_lengths.bin")  # gzip members in the reference
+ENCODER_FILES = ("read_pos.bin", "read_noise.txt", "read_noisepos.bin", "read_order.bin", "read_rev.txt",
+                 "read_lengths.bin", "read_unaligned.txt", "read_unaligned.txt.count")
+
+
+def reorder_file_set(read, ln, L, res):
+    """What reorder_main<N> leaves in temp_dir for the reorder result `res` (oracle or GPU streams dict), with the four
+    gzip files uncompressed: -> {file name: bytes}."""
+    toff = [int(x) for x in res["tid_off"]]
+    out = {}
+    for t, (a, b) in enumerate(zip(toff[:-1], toff[1:])):
+        out["read_order.bin.%d" % t] = np.asarray(res["order"][a:b], np.uint32).tobytes()
+        out["read_rev.txt.%d" % t] = np.asarray(res["rc"][a:b], np.uint8).tobytes()
+        out["tempflag.txt.%d" % t] = np.asarray(res["flag"][a:b], np.uint8).tobytes()
+        out["temppos.txt.%d" % t] = np.asarray(res["pos"][a:b], np.int64).tobytes()
+        out["read_lengths.bin.%d" % t] = np.asarray(res["rlen"][a:b], np.uint16).tobytes()
+        out["temp.dna.%d" % t] = po.write_dna_stream(read, ln, L, res["order"][a:b], res["rc"][a:b])
+    out["temp.dna.singleton"] = po.write_dna_stream(read, ln, L, res["order_s"], None)
+    out["read_order.bin.singleton"] = np.asarray(res["order_s"], np.uint32).tobytes()
+    out["temp.dna.singleton.count"] = np.array([len(res["order_s"])], np.uint32).tobytes()
+    return out
+
+
+def pack_seq(seq: bytes):
+    """pack_compress_seq's 2-bit packing (encoder.cpp:133-147, orc_pack_seq) -> (packed bytes, tail bytes)."""
+    import ctypes as C
+    Lo = po.lib()
+    Lo.orc_pack_seq.restype = C.c_uint64
+    Lo.orc_pack_seq.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p]
+    buf, tail = np.zeros(max(len(seq) // 4, 1), np.uint8), np.zeros(4, np.uint8)
+    nb = Lo.orc_pack_seq(seq, len(seq), buf.ctypes.data, tail.ctypes.data)
+    return buf[:nb].tobytes(), tail[:len(seq) % 4].tobytes()
+
+
+def encoder_file_set(enc, packed_suffix=".raw"):
+    """What encoder_main<N> leaves in temp_dir for the encoder result `enc` (po.encode / EncoderStage.streams dict):
+    -> {file name: bytes}; read_seq.bin.<t> as the packed bytes (`packed_suffix`: ".raw" = the reference's .bsc
+    inflated, ".tmp" = what spring_encoder_run leaves) + ".tail"."""
+    out = {"read_pos.bin": np.asarray(enc["pos"], np.uint64).tobytes(), "read_noise.txt": bytes(enc["noise"]),
+           "read_noisepos.bin": np.asarray(enc["noisepos"], np.uint16).tobytes(),
+           "read_order.bin": np.asarray(enc["order"], np.uint32).tobytes(),
+           "read_rev.txt": np.asarray(enc["rc"], np.uint8).tobytes(),
+           "read_lengths.bin": np.asarray(enc["rlen"], np.uint16).tobytes(),
+           "read_unaligned.txt": bytes(enc["unaligned"]),
+           "read_unaligned.txt.count": np.array([enc["len_unaligned"]], np.uint64).tobytes()}
+    off = 0
+    for t, sl in enumerate(int(x) for x in enc["seq_len_tid"]):
+        packed, tail = pack_seq(enc["seq"][off:off + sl])
+        out["read_seq.bin.%d%s" % (t, packed_suffix)] = packed
+        out["read_seq.bin.%d.tail" % t] = tail
+        off += sl
+    return out
+
+
 def check_invariants(res, read, ln, L, n):
     """Properties every legal reorder output has (any chain count)."""
     order, order_s = res["order"], res["order_s"]

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import readsets as rs
-from helpers import GOLDEN, KEYS, SMALL_SETS, check_invariants, named_set
+from helpers import GOLDEN, KEYS, SMALL_SETS, check_invariants, early_stop_set, named_set
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
@@ -732,24 +732,11 @@ def test_1M_150bp_k1_reference_counters_on_the_gpu():
     assert st["probes"] == 92_923_476 and st["cands"] == 996_385
 
 
-def _early_stop_set():
-    """40 k reads of a small genome (25x) in the middle of 525 k unrelated random reads.  Chain 0 starts at read 0
-    (unrelated) and new seeds come from the top of the pool, so 520 k unrelated reads -- two failed searches each --
-    are consumed first: at iteration 1 000 000 more than half of the last million were unmatched and the search
-    stops (reorder.h:433-439) before the related reads are reached."""
-    L = 100
-    rng = np.random.default_rng(2024)
-    rel = rs.np_reads(5, 40_000 * L // 25, 40_000, L, 0.01)
-    unrel = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, (525_000, L))]
-    a = np.concatenate([unrel[:5000], rel, unrel[5000:]]).astype(np.uint8)
-    return rs.pack_fixed(a), a.shape[0], L, rs.pack_fixed(rel)
-
-
 def test_early_stop_fires_on_both_sides():
     """STOP_CRITERIA_REORDER (reorder.h:433-439, params.h): K = 1, > 50 % of the first million iterations unmatched
     -> stop_searching; every read left after that is emitted as a singleton without a search."""
     sa = _sa()
-    dna, n, L, rel_dna = _early_stop_set()
+    dna, n, L, rel_dna = early_stop_set()
     read, ln = po.load_dna(dna, n, L)
     want = po.reorder_serial(read, ln, L)
     # the stop fired in the oracle: exactly one million iterations searched (50 shifts x 2 directions each), and the
