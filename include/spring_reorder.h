@@ -104,6 +104,13 @@ typedef struct {
                              front to back.  1 = a key pass over the unpacked reads, a memset of the
                              table, the merged list of both dictionaries and the insert pass over it.  stats.dict_build_path
                              says what ran.  Anything else is refused by spring_reorder_create */
+  int32_t strand_filter;    /* four-chain round kernel with the known-absent masks: a second, small, probe-only table of the
+                             canonical dictionary windows answers "is W a key of dictionary 0 / 1, and is
+                             its reverse complement?" in one fetch, and a chain whose seed has no match yet sweeps its windows
+                             through it before it searches.  It can only ever prove a key absent: same results.  0 = the
+                             library's choice (on wherever the masks are on: hash-addressed table, reads up to 192 bases,
+                             k_round_mc), -1 = off, n > 0 = on with at most 2^n buckets (tests: a tiny table whose buckets are
+                             nearly all full).  Anything else (< -1, > 32) is refused by spring_reorder_create */
 } spring_reorder_opts;
 
 typedef struct {
@@ -139,6 +146,8 @@ typedef struct {
   uint64_t sort_list_overflows;/* ... of those: because more hash changes inside runs were found than the repair's list holds */
   uint64_t dict_build_path;    /* last dictionary build: bit 0 = the keys came from the unpack pass (clear: a key pass over the
                                   reads), bit 1 = the table was written in one pass (clear: memset, merge and insert passes) */
+  uint64_t strand_filter;      /* 1: the chain phase ran the presence-table sweep (opts.strand_filter) */
+  uint64_t strand_filter_dropped; /* keys the presence table does not hold because their bucket was full (last dictionary built) */
 } spring_reorder_stats;
 
 void spring_reorder_default_opts(spring_reorder_opts *o);

@@ -63,7 +63,7 @@ class Opts(C.Structure):
                 ("table_mode", C.c_int32), ("plan0", C.c_int32 * 6), ("plan1", C.c_int32 * 6), ("long_min", C.c_int32),
                 ("long_blocks", C.c_int32), ("debug", C.c_int32), ("long_split", C.c_int32), ("entry_flags", C.c_int32),
                 ("out_writers", C.c_int32), ("alternatives", C.c_int32), ("phases", C.c_int32), ("known_absent", C.c_int32),
-                ("sort_prefix_bits", C.c_int32), ("dict_build_mode", C.c_int32)]
+                ("sort_prefix_bits", C.c_int32), ("dict_build_mode", C.c_int32), ("strand_filter", C.c_int32)]
 
 
 class FastqInfo(C.Structure):
@@ -157,7 +157,8 @@ class Stats(C.Structure):
                    ("table_minz", C.c_uint64), ("table_marked_lines", C.c_uint64), ("long_splits", C.c_uint64), ("alternatives", C.c_uint64), ("phases", C.c_uint64),
                    ("ms_search_busy", C.c_double),
                    ("sort_prefix_bits", C.c_uint64), ("sort_repaired_runs", C.c_uint64), ("sort_full_sorts", C.c_uint64),
-                   ("sort_long_runs", C.c_uint64), ("sort_list_overflows", C.c_uint64), ("dict_build_path", C.c_uint64)])
+                   ("sort_long_runs", C.c_uint64), ("sort_list_overflows", C.c_uint64), ("dict_build_path", C.c_uint64),
+                   ("strand_filter", C.c_uint64), ("strand_filter_dropped", C.c_uint64)])
 
     def asdict(self):
         d = {}

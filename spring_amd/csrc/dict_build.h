@@ -35,6 +35,13 @@ void launch_tab_overflow_blocks(hipStream_t st, const uint64_t *h0, uint32_t nk0
 void launch_tab_overflow_pairs(hipStream_t st, const uint64_t *h0, uint32_t nk0, const uint64_t *h1, DictBuild d0,
                                DictBuild d1, uint32_t *fpt, int bshift, const uint32_t *ovf, uint32_t novf);
 
+// ---- the strand-symmetric presence table (strand_filter.h): 2^lgb buckets of four 32-bit slots at pres, zeroed by the
+// caller.  Every unique key of both dictionaries (h0 / h1: their sorted unique hashes, windows of wl bases) is entered
+// under its canonical form; drops: PRES_DROP_CTRS zeroed counters whose sum is the number of keys that met a full bucket.
+constexpr uint32_t PRES_DROP_CTRS = 1024;
+void launch_pres_insert(hipStream_t st, const uint64_t *h0, uint32_t nk0, const uint64_t *h1, uint32_t nk1, int wl, uint32_t *pres,
+                        int lgb, uint32_t *drops);
+
 }  // namespace sr
 
 #endif

@@ -7,11 +7,13 @@
 //   k_tab_write          one workgroup per block of buckets builds the block's image in LDS and stores it in full
 //                        lines -- no memset of the table, no merged list of the two dictionaries (merge_by_hash)
 //   k_tab_overflow_blocks / _pairs  the pairs past the fourth of a bucket claim a free slot further on (CAS), as before
+//   k_pres_insert        the strand-symmetric presence table (strand_filter.h): one slot per canonical window
 // The table they produce answers every lookup as the one k_tab_insert builds (reorder_kernels.hip): same tags, same
 // payloads, the same pairs in the home buckets.
 #include <hip/hip_runtime.h>
 
 #include "dict_build.h"
+#include "strand_filter.h"
 
 namespace sr {
 
@@ -322,6 +324,47 @@ void launch_tab_overflow_pairs(hipStream_t st, const uint64_t *h0, uint32_t nk0,
                                DictBuild d1, uint32_t *fpt, int bshift, const uint32_t *ovf, uint32_t novf) {
   if (!novf) return;
   hipLaunchKernelGGL(k_tab_overflow_pairs, dim3((novf + 255) / 256), dim3(256), 0, st, h0, nk0, h1, d0, d1, fpt, bshift, ovf);
+}
+
+// ------------------------------------------------ the strand-symmetric presence table (strand_filter.h)
+// One thread per unique key of either dictionary (h = mix64(key): the sorted unique-hash arrays the main table is built
+// from, so every key of the main table is covered).  The slot of canon(key) is claimed with one CAS that already carries
+// the key's flag; a thread that finds the fingerprint there ORs its flag in.  Keys that meet a full bucket are counted per
+// workgroup in LDS and added to one of PRES_DROP_CTRS counters: no same-address atomic per dropped key.
+__global__ __launch_bounds__(256) void k_pres_insert(const uint64_t *__restrict__ h0, uint32_t nk0, const uint64_t *__restrict__ h1,
+                                                     uint32_t nk1, int wl, uint32_t *__restrict__ pres, int lgb,
+                                                     uint32_t *__restrict__ drops) {
+  __shared__ uint32_t s_drop;
+  if (threadIdx.x == 0) s_drop = 0u;
+  __syncthreads();
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < (uint64_t)nk0 + nk1) {
+    const int l = t >= nk0 ? 1 : 0;
+    const uint64_t key = db_unmix64(l ? h1[t - nk0] : h0[t]);
+    uint32_t flags;
+    const uint64_t hc = sf::mix64(sf::canon_and_flags(key, wl, l, flags));
+    const uint32_t fp = sf::fp_of(hc), word = (fp << 4) | flags;
+    uint32_t *bk = pres + 4ull * sf::bucket_of(hc, lgb);
+    bool placed = false;
+    for (int sl = 0; sl < 4 && !placed; sl++) {
+      uint32_t old = __hip_atomic_load(bk + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (old == 0u) old = atomicCAS(bk + sl, 0u, word);
+      if (old == 0u) placed = true;
+      else if ((old >> 4) == fp) {
+        if ((old & word & 15u) != (word & 15u)) atomicOr(bk + sl, word & 15u);
+        placed = true;
+      }
+    }
+    if (!placed) atomicAdd(&s_drop, 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_drop) atomicAdd(drops + (blockIdx.x & (PRES_DROP_CTRS - 1u)), s_drop);
+}
+void launch_pres_insert(hipStream_t st, const uint64_t *h0, uint32_t nk0, const uint64_t *h1, uint32_t nk1, int wl, uint32_t *pres,
+                        int lgb, uint32_t *drops) {
+  const uint64_t nt = (uint64_t)nk0 + nk1;
+  if (!nt) return;
+  hipLaunchKernelGGL(k_pres_insert, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, h0, nk0, h1, nk1, wl, pres, lgb, drops);
 }
 
 }  // namespace sr

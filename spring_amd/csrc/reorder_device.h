@@ -164,6 +164,10 @@ struct DevParams {
   int mc;                    // 1: four chains per wavefront (k_round_mc) where it applies
   int ka, ka_lo;             // ka = 1: k_round_mc's chains keep known-absent window masks (reorder_round_mc.h: search_ka); four limbs per
                              // strand live in Chain::revref[8..15] between rounds, the forward strand's from limb ka_lo
+  // sf = 1 (only with ka): the strand-symmetric presence table (strand_filter.h) -- 2^pres_lgb buckets of four 32-bit slots at
+  // pres -- and a chain whose seed has no match yet sweeps its windows through it before it searches (sweep_ka)
+  const uint4 *pres;
+  int pres_lgb, sf;
   // k_round_mc runs chains of one class per wavefront (the four chains of a wavefront take the union of their
   // paths): k_mg_mark sorts the running local chains of every block of MARK_BLOCK consecutive chain ids by what the
   // next round will ask of them -- 0 left search after a failed right search, 1 first search of a new seed, 2 search

@@ -11,6 +11,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "reorder_device.h"
+#include "strand_filter.h"
 #include "synth_common.h"
 
 namespace sr {

@@ -148,6 +148,8 @@ struct spring_reorder_ctx {
   int bshift = 63;        // plain home bucket = hash >> bshift (nb = 2^(64 - bshift) buckets)
   int minz = 0, lshift = 31;  // minimizer-addressed table (TabView)
   uint32_t marked_lines = 0;  // ... lines of it whose keys were sent to the redirect address
+  uint4 *pres = nullptr;      // the strand-symmetric presence table (strand_filter.h): 2^pres_lgb buckets of 16 bytes; null: not built
+  int pres_lgb = 0;
   bool user_plan0 = false;    // opts.plan0 was given (fill_params)
   DevParams P;
   uint32_t K = 0;
@@ -375,6 +377,8 @@ int spring_reorder_create(spring_reorder_ctx **out, const spring_reorder_opts *o
     return fail(SPRING_REORDER_E_ARG, "sort_prefix_bits: 0 (library's choice) or 1 .. 64 bits of the key hash (64 = the full sort)");
   if (o.dict_build_mode < 0 || o.dict_build_mode > 1)
     return fail(SPRING_REORDER_E_ARG, "dict_build_mode: 0 (library's choice) or 1 (key pass, memset, merge and insert passes)");
+  if (o.strand_filter < -1 || o.strand_filter > 32)
+    return fail(SPRING_REORDER_E_ARG, "strand_filter: 0 (library's choice), -1 (off) or 1 .. 32 (on, at most 2^n buckets)");
   int ndev = 0;
   HIPCHK(hipGetDeviceCount(&ndev));
   if (ndev <= 0) return fail(SPRING_REORDER_E_HIP, "no HIP device");
@@ -1077,6 +1081,7 @@ static TabView tab_view(const spring_reorder_ctx *ctx) {
 // handful of short runs for the repair -- where T = 32 would leave 1.2 M / 18.6 M.  rocPRIM sorts 8 bits per pass here.
 static unsigned sort_prefix_auto(uint64_t m) { return m <= (1ull << 29) ? 40u : 48u; }
 
+static bool strand_filter_wanted(const spring_reorder_ctx *ctx);
 int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
   double t_last = now_ms();
   if (!ctx) return fail(SPRING_REORDER_E_ARG, "ctx is NULL");
@@ -1375,6 +1380,44 @@ int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
     ctx->dfree(mv0); ctx->dfree(mh); ctx->dfree(mv); ctx->dfree(d_tmp);
     ctx->dfree(bk_in); ctx->dfree(bk_out); ctx->dfree(tp_in); ctx->dfree(tp_out); ctx->dfree(d_tmp2); ctx->dfree(d_marked); ctx->dfree(d_ovf);
   }
+  // ---- the strand-symmetric presence table (strand_filter.h; opts.strand_filter), only where the chain phase will read it.
+  // Size: at least one bucket per key, the next power of two -- between 0.5 and 1 keys per four-slot bucket (a load of
+  // 0.125 .. 0.25; fewer where a window and its reverse complement are both keys: they share a slot).  Keys fall into
+  // buckets like a Poisson variable of that mean: 0.18 % .. 1.9 % of the buckets are full, and a full bucket costs a
+  // lookup nothing but its answer (the main table is asked as before).  16 bytes a bucket: 4.3 GB for the 194 M keys of
+  // 100 M reads of 150 bases (0.72 keys per bucket: 0.6 % full), against the 17 GB of the main table.
+  ctx->pres = nullptr; ctx->pres_lgb = 0;
+  ctx->stats.strand_filter = 0; ctx->stats.strand_filter_dropped = 0;
+  int lgb = 0;
+  if (nm && nm < 0xffffffffull && strand_filter_wanted(ctx)) {
+    while (lgb < 32 && (1ull << lgb) < nm) lgb++;
+    if (ctx->o.strand_filter > 0) lgb = std::min(lgb, ctx->o.strand_filter);
+    // The table only saves work: a pool that fits without it must not fail for it.  No room: the chain phase runs without
+    // the sweep (setup_chains sees no table; stats.strand_filter = 0).
+    if (ctx->dmalloc((void **)&ctx->pres, (size_t)16 << lgb)) {
+      (void)hipGetLastError();
+      ctx->pres = nullptr;
+      if (dbg) fprintf(stderr, "[dict] presence table: no room for 2^%d buckets, running without\n", lgb);
+    }
+  }
+  if (ctx->pres) {
+    uint32_t *d_drops = nullptr;
+    std::vector<uint32_t> h_drops(PRES_DROP_CTRS);
+    DMALLOC(d_drops, PRES_DROP_CTRS * 4);
+    HIPCHK(hipMemsetAsync(ctx->pres, 0, (size_t)16 << lgb, st));
+    HIPCHK(hipMemsetAsync(d_drops, 0, PRES_DROP_CTRS * 4, st));
+    launch_pres_insert(st, uhash[0], (uint32_t)nk0, uhash[1], (uint32_t)nk1, ctx->dict[0].end - ctx->dict[0].start + 1,
+                       reinterpret_cast<uint32_t *>(ctx->pres), lgb, d_drops);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h_drops.data(), d_drops, PRES_DROP_CTRS * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (uint32_t v : h_drops) ctx->stats.strand_filter_dropped += v;
+    ctx->pres_lgb = lgb;
+    ctx->dfree(d_drops);
+    if (dbg) fprintf(stderr, "[dict] presence table: 2^%d buckets, %llu of %llu keys dropped\n", lgb,
+                     (unsigned long long)ctx->stats.strand_filter_dropped, (unsigned long long)nm);
+    DBG_T("presence table");
+  }
   for (int l = 0; l < 2; l++) { ctx->dfree(uhash[l]); ctx->dfree(ustart[l]); ctx->dfree(ucount[l]); }
   DBG_T("free temps");
   HIPCHK(hipEventRecord(ctx->ev[3], st));
@@ -1459,6 +1502,62 @@ static bool dict_is_very_deep(const spring_reorder_ctx *ctx) {
   const uint64_t big = (uint64_t)ctx->dict[0].big_reads + ctx->dict[1].big_reads, nd = (uint64_t)ctx->dict[0].numreads + ctx->dict[1].numreads;
   return dict_is_deep(ctx) && nd > 0 && big * 4 >= nd;
 }
+// the known-absent window masks (reorder_round_mc.h: search_ka) fit this pool: reads up to 192 bases -- four limbs per strand in
+// the spare half of Chain::revref, the forward strand's from the limb of its first window (offsets dstart[0] .. L - wl)
+static bool ka_layout_ok(const spring_reorder_ctx *ctx, int *ka_lo) {
+  if (ctx->Lpad > 192 || ctx->o.known_absent < 0 || ctx->minz) return false;
+  const int wlen = ctx->dict[0].end - ctx->dict[0].start + 1, lo = ctx->dict[0].start >> 5;
+  if (wlen <= 32 && ctx->dict[1].start == ctx->dict[0].end + 1 && ctx->dict[1].end - ctx->dict[1].start + 1 == wlen &&
+      2 * (ctx->L - wlen) + 2 <= 64 * (lo + 4) && 2 * ctx->dict[1].start + 2 <= 256 && lo + 4 <= 6) {
+    if (ka_lo) *ka_lo = lo;
+    return true;
+  }
+  return false;
+}
+static uint32_t auto_chains(uint32_t n, bool deep, bool very_deep, bool heavy_tail);
+// ---- the rules setup_chains picks the round kernel by, in one place: build_dict asks them too (strand_filter_wanted)
+// the deep-bin kernel variants: opts.deep_bins = 1 / -1 forces them on / off; the second candidate of opts.alternatives = 2
+// is found by them
+static bool deep_kernel_chosen(const spring_reorder_ctx *ctx) {
+  const spring_reorder_opts &o = ctx->o;
+  return (o.deep_bins ? o.deep_bins > 0 : dict_wants_deep_kernel(ctx)) || o.alternatives == 2;
+}
+// two chain groups are possible on a pool of n reads and Ktot chains (the pool-independent part of setup_chains' test)
+static uint32_t group_half(uint32_t Ktot) {  // group 0 = chains [0, half): Ktot / 2 to the nearest multiple of 2048
+  return (uint32_t)std::max<uint64_t>((((uint64_t)Ktot / 2 + 1024) / 2048) * 2048, 2048);
+}
+static uint32_t group_nmid(uint32_t n) { return (uint32_t)(((uint64_t)n / 2) >> UBLK_SHIFT << UBLK_SHIFT); }  // group 1's seeds: reads [0, nmid)
+static bool two_groups_fit(uint32_t n, uint32_t Ktot) {
+  const uint32_t half = group_half(Ktot), nmid = group_nmid(n);
+  return Ktot >= 4096 && half < Ktot && n < 0x80000000u && nmid > 0 && n >= Ktot;
+}
+static bool two_groups_pay_shallow(uint32_t Ktot) { return Ktot >= 16384; }  // (shallow dictionaries; evidence in setup_chains)
+// groups asked for: opts.phases, or the library's choice -- two where they pay and the count is a multiple of 2048
+static int groups_wanted(const spring_reorder_opts &o, uint32_t Ktot, bool pays) {
+  return o.phases > 0 ? o.phases : (pays && Ktot % 2048 == 0 ? 2 : 1);
+}
+// four chains per wavefront (k_round_mc) for a context that runs K chains in `phases` groups (evidence in setup_chains):
+// opts.fused = 2 never, opts.fused = 3 whatever the count, else from 32 768 chains on with two groups (20 480 with the masks
+// on dictionaries of < 1.05 reads per key), 49 152 with one; never beyond 2^32 buckets (bucket indices in 32 bits)
+static bool mc_kernel_chosen(const spring_reorder_ctx *ctx, uint32_t K, int phases, bool ka_ok) {
+  if (ctx->o.fused == 2 || 64 - ctx->bshift > 32) return false;
+  const uint64_t nd = (uint64_t)ctx->dict[0].numreads + ctx->dict[1].numreads, nk = (uint64_t)ctx->dict[0].numkeys + ctx->dict[1].numkeys;
+  const uint32_t mc_min = phases == 2 ? ((ka_ok && nd * 100 < nk * 105) ? 20480u : 32768u) : 49152u;
+  return K >= mc_min || ctx->o.fused == 3;
+}
+// build_dict asks: will the chain phase read the presence table (opts.strand_filter)?  setup_chains' own rules (above) on
+// what is known when the dictionary is built: the chain count is opts.num_chains or the default rule's, one context.  (A
+// pool whose ranks are given another count at mg_begin runs without the table where this says no, and holds a table it
+// does not read where this says yes -- same results either way; setup_chains decides what runs and reports it.)
+static bool strand_filter_wanted(const spring_reorder_ctx *ctx) {
+  const spring_reorder_opts &o = ctx->o;
+  if (o.strand_filter < 0 || !ka_layout_ok(ctx, nullptr)) return false;
+  const bool fused = !o.force_literal_update && o.fused >= 0;
+  if (!fused || o.collect_stats || deep_kernel_chosen(ctx)) return false;
+  const uint32_t K = o.num_chains ? o.num_chains : auto_chains(ctx->n, dict_is_deep(ctx), dict_is_very_deep(ctx), dict_has_heavy_tail(ctx));
+  const int phases = (groups_wanted(o, K, two_groups_pay_shallow(K)) == 2 && two_groups_fit(ctx->n, K)) ? 2 : 1;
+  return mc_kernel_chosen(ctx, K, phases, true);
+}
 static void fill_params(spring_reorder_ctx *ctx, DevParams &P) {
   const spring_reorder_opts &o = ctx->o;
   P.reads = ctx->d_reads; P.lens = ctx->d_lens; P.n = ctx->n;
@@ -1503,8 +1602,7 @@ static void fill_params(spring_reorder_ctx *ctx, DevParams &P) {
   P.tab = tab_view(ctx);
   // deep data (>= 1.3 reads per dictionary key on average: coverage of a few hundred x and up): the chain kernel
   // trims dead bin tails while it scans; opts.deep_bins = 1 / -1 forces the variant on / off (same results)
-  P.deep_bins = o.deep_bins ? (o.deep_bins > 0) : dict_wants_deep_kernel(ctx);
-  if (o.alternatives == 2) P.deep_bins = 1;  // (the second candidate is found by the deep-bin variants of the round kernel)
+  P.deep_bins = deep_kernel_chosen(ctx) ? 1 : 0;
   // ... and the next read of a chain sits at shift 0 or 1 nearly always, while every verified bin a batch holds past the
   // winner is scanned for nothing: a narrow first batch (2 + 6 + 8 + 16 shifts instead of 4 + 8 + 16: 1 600x -3 %, 6 400x
   // -4 %, 25 600x -7 %, PhiX-like -5 %; 1 + 3 + 4 + 8 + 16 the same within 1 %, 1 + 1 + 2 + 4 + 8 + 16 slower at 400x)
@@ -1561,7 +1659,7 @@ static void fill_params(spring_reorder_ctx *ctx, DevParams &P) {
 // Pools with a heavy tail of bins (dict_has_heavy_tail; shallow on average): a round lasts as long as its longest bin scans
 // whatever the chain count, so more chains per round are nearly free: 20 M genome-like reads, chains stage 1 453 / 737 /
 // 511 / 483 ms with 19 531 / 65 536 / 131 072 / 262 144 chains (profiles/r04_genomic.txt) -- n / 128 up to 131 072 as well.
-static uint32_t auto_chains(uint32_t n, bool deep, bool very_deep, bool heavy_tail = false) {
+static uint32_t auto_chains(uint32_t n, bool deep, bool very_deep, bool heavy_tail) {
   uint64_t k = (deep || heavy_tail) ? n >> 7 : n >> 10;
   const uint64_t cap = ((deep && !very_deep) || (heavy_tail && !deep)) ? 131072 : 65536;
   if (k < 1) k = 1;
@@ -1616,15 +1714,15 @@ static int setup_chains(spring_reorder_ctx *ctx, uint32_t K, uint32_t c0, uint32
     // (the groups are cut from the GLOBAL chain ids, so a pool's output does not depend on the number of ranks: group 0 = chains
     // [0, half), half = Ktot / 2 to the nearest multiple of 2048; a rank of a pool owns an equal slice of each group)
     const uint32_t world = K ? Ktot / K : 1, rank = K ? c0 / K : 0;
-    const uint32_t half = (uint32_t)std::max<uint64_t>((((uint64_t)Ktot / 2 + 1024) / 2048) * 2048, 2048);
-    const uint32_t nmid = (uint32_t)(((uint64_t)n / 2) >> UBLK_SHIFT << UBLK_SHIFT);  // group 1's seeds: reads [0, nmid)
+    const uint32_t half = group_half(Ktot);
+    const uint32_t nmid = group_nmid(n);  // group 1's seeds: reads [0, nmid)
     // (n >= Ktot: every chain starts with a seed of its own, reorder.h:405-421 -- with fewer reads than chains only chain 0 runs, the
     // second group would have no chain at all and nobody would ever pick the seeds of its range)
     // (world = 1: the whole pool, as run_chains runs it -- whoever owns the proposal buffer.  The words of both groups live in
     // one buffer of Ktot words either way, and the output must not depend on who allocated it)
     const bool pool_ok = world == 1 ? c0 == 0
                                     : ((uint64_t)K * world == Ktot && half % (MARK_BLOCK * world) == 0 && (Ktot - half) % (MARK_BLOCK * world) == 0);
-    const bool can = allow_phases && fused && K > 0 && pool_ok && Ktot >= 4096 && half < Ktot && n < 0x80000000u && nmid > 0 && n >= Ktot;
+    const bool can = allow_phases && fused && K > 0 && pool_ok && two_groups_fit(n, Ktot);
     // Deep-bin pools (one chain per wavefront, up to 131 072 chains), one group / two, chains stage in ms: 20 M reads (131 072 chains)
     // 400x 112 / 102, 1 600x 122 / 115, 6 400x 136 / 131, 25 600x (two candidates per proposal) 151 / 150; 10 M reads (78 125 chains)
     // 400x 60 / 58, 6 400x 74 / 79, 25 600x 85 / 90; 5 M reads (39 062) 34 / 35, 44 / 50, 55 / 59; 2.5 M reads (19 531) 21 / 26,
@@ -1634,11 +1732,11 @@ static int setup_chains(spring_reorder_ctx *ctx, uint32_t K, uint32_t c0, uint32
     // 1 475 / 1 619 -- blocks of 4-8 wavefronts starve beside the other group's one-wavefront workgroups.
     // (the rule looks at the pool -- Ktot, the dictionary --, never at a rank's share: the choice changes the output)
     const bool long_kernels = P.deep_bins && P.long_budget > 0;
-    const bool pays = P.deep_bins ? (Ktot >= 131072 && P.alts == 1 && !long_kernels) : Ktot >= 16384;
+    const bool pays = P.deep_bins ? (Ktot >= 131072 && P.alts == 1 && !long_kernels) : two_groups_pay_shallow(Ktot);
     // (the library's own choice also asks for a multiple of 2048 chains -- which the default chain count is from 16 384 on --
     // whatever the number of ranks: both groups then split evenly over 1, 2, 4 or 8 ranks into slices of whole mark-step
     // blocks, and the choice -- one group or two -- is the same for all of them)
-    const int want = ctx->o.phases > 0 ? ctx->o.phases : (pays && Ktot % 2048 == 0 ? 2 : 1);
+    const int want = groups_wanted(ctx->o, Ktot, pays);
     if (ctx->o.phases > 2) return fail(SPRING_REORDER_E_ARG, "phases: 0 (library's choice), 1 or 2");
     if (ctx->o.phases == 2 && !can)
       return fail(SPRING_REORDER_E_ARG, "phases = 2 needs the fused round (fused >= 0, no literal consensus path), at least 4096 "
@@ -1676,7 +1774,7 @@ static int setup_chains(spring_reorder_ctx *ctx, uint32_t K, uint32_t c0, uint32
   const size_t nchunk = cap / CHUNK + 2;
   DMALLOC(P.e_rec, cap * sizeof(uint4)); DMALLOC(P.e_chunk, nchunk * sizeof(uint2));
   DMALLOC(P.s_rec, cap * 4); DMALLOC(P.s_chunk, nchunk * sizeof(uint2));
-  P.mc = ctx->o.fused == 2 ? 0 : 1;  // opts.fused = 2: one chain per wavefront everywhere (A/B, tests)
+  // (opts.fused = 2: one chain per wavefront everywhere -- A/B, tests; the rule itself is mc_kernel_chosen, below the evidence)
   // Four chains per wavefront pay when a launch holds several wavefronts per slot (5 120 slots of four chains): with
   // fewer chains the GPU is not full and every wavefront waits for the slowest of its four.  25x, chains stage, four
   // chains / one chain per wavefront: 4 882 chains (5 M reads) 74 / 47 ms, 19 531 (20 M) 106 / 100, 39 062 (40 M)
@@ -1684,25 +1782,20 @@ static int setup_chains(spring_reorder_ctx *ctx, uint32_t K, uint32_t c0, uint32
   // kernel's lead below 40 000 chains is 5-16 %)
   // known-absent window masks (reorder_round_mc.h: search_ka): reads up to 192 bases -- four limbs per strand in the spare
   // half of Chain::revref, the forward strand's from the limb of its first window (offsets dstart[0] .. L - wl)
-  bool ka_ok = false;
   int ka_lo = 0;
-  if (P.Lpad <= 192 && ctx->o.known_absent >= 0 && !ctx->minz) {
-    const int wlen = ctx->dict[0].end - ctx->dict[0].start + 1, lo = ctx->dict[0].start >> 5;
-    if (wlen <= 32 && ctx->dict[1].start == ctx->dict[0].end + 1 && ctx->dict[1].end - ctx->dict[1].start + 1 == wlen &&
-        2 * (ctx->L - wlen) + 2 <= 64 * (lo + 4) && 2 * ctx->dict[1].start + 2 <= 256 && lo + 4 <= 6) {
-      ka_ok = true; ka_lo = lo;
-    }
-  }
+  const bool ka_ok = ka_layout_ok(ctx, &ka_lo);
   // Round 6, with the masks (chains stage, 25x pools, one chain / four chains per wavefront, two groups): 14 648 chains 82 / 79 ms,
   // 18 432 99 / 101, 22 528 114 / 110, 28 672 130 / 112; at 100x (1.09 reads per key: most probes find their key, the masks
   // save little) 108 / 129, 123 / 141, 131 / 139 -- so on very shallow dictionaries (< 1.05 reads per key) the four-chain
   // kernel takes over at 20 480 chains instead of 32 768 (profiles/r06_mc_threshold.txt)
-  const uint64_t nd_ = (uint64_t)ctx->dict[0].numreads + ctx->dict[1].numreads, nk_ = (uint64_t)ctx->dict[0].numkeys + ctx->dict[1].numkeys;
-  const uint32_t mc_min = P.phases == 2 ? ((ka_ok && nd_ * 100 < nk_ * 105) ? 20480u : 32768u) : 49152u;
-  if (K < mc_min && ctx->o.fused != 3) P.mc = 0;   // (opts.fused = 3: four chains per wavefront whatever the count -- tests)
-  if (64 - ctx->bshift > 32) P.mc = 0;            // (k_round_mc keeps bucket indices in 32 bits)
+  P.mc = mc_kernel_chosen(ctx, K, P.phases, ka_ok) ? 1 : 0;
   P.ka = (P.mc && ka_ok) ? 1 : 0;
   P.ka_lo = P.ka ? ka_lo : 0;
+  // ... and the presence table's sweep (sweep_ka) where build_dict made the table and k_round_mc<.., KA> is what runs
+  P.sf = (P.ka && ctx->pres && fused && !ctx->o.collect_stats && !P.deep_bins) ? 1 : 0;
+  P.pres = P.sf ? ctx->pres : nullptr;
+  P.pres_lgb = P.sf ? ctx->pres_lgb : 0;
+  ctx->stats.strand_filter = (uint64_t)P.sf;
   if (ctx->minz && !(fused && P.mc && !ctx->o.collect_stats && !P.deep_bins))
     return fail(SPRING_REORDER_E_ARG, "table_mode = 2 (minimizer-addressed table) is an experiment of the four-chain round kernel: "
                 "shallow dictionary, at least 49152 chains or fused = 3, no work counters");

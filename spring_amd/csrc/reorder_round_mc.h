@@ -1012,12 +1012,85 @@ __device__ __forceinline__ void batch_ka(const DevParams &P, GLds<NQ, KA> &S, ld
   }
 }
 
+// ---- the sweep through the strand-symmetric presence table (DevParams::sf; strand_filter.h has the layout and the
+// exactness argument).  revref is the reverse complement of ref[0, ref_len): the window at offset o' of revref is the
+// reverse complement of the ref window at offset ref_len - wl - o', and a failing search of a lone seed asks the main table
+// about both, under two names.  One bucket of the presence table answers "is W a key of dictionary 0 / 1, and is rc(W)?".
+// So before a chain whose seed has no match yet forms its need words, lane gl takes the ref offsets o_min + gl + 16 i that
+// some still-unknown code of either strand asks about, fetches the bucket of canon(W_o) -- at most KA_M in flight, as in
+// batch_ka -- and ORs every PROVEN absence into S.ka[0] at o and S.ka[1] at ref_len - wl - o, both dictionaries each.
+// It can only add true "absent" bits (a full bucket or a fingerprint with the flag set says nothing): the search that
+// follows skips what is known and asks the main table about the rest, exactly as before.
 template <int NQ, bool KA>
-__device__ __forceinline__ void search_ka(const DevParams &P, GLds<NQ, KA> &S, lds_u32_t *stage, int ref_len, int wide, int lane, int gl,
-                                          int &wcode, uint32_t &wrid) {
+__device__ __forceinline__ void sweep_ka(const DevParams &P, GLds<NQ, KA> &S, int ref_len, int gl) {
+  constexpr int LDS_PAD = GLds<NQ, KA>::PAD;
+  const uint64_t *sref = S.refs[0] + LDS_PAD;
+  const int wl = P.wl, top = ref_len - wl;  // a strand's windows: offsets [0, top]
+  const uint64_t kmask = 2 * wl < 64 ? ((1ull << (2 * wl)) - 1) : ~0ull;
+  // ref offsets [lo, hi) whose window stream (rev, l) asks about: forward dstart[l] + shift, reverse top - (dstart[l] - shift)
+  int f0lo, f0hi, f1lo, f1hi, r0lo, r0hi, r1lo, r1hi;
+  {
+    const int ds0 = uni_i32(P.dstart[0]), ds1 = uni_i32(P.dstart[1]);
+    int lo, hi;
+    ka_valid_shifts(P, 0, 0, ref_len, lo, hi); f0lo = ds0 + lo; f0hi = ds0 + hi;
+    ka_valid_shifts(P, 1, 0, ref_len, lo, hi); f1lo = ds1 + lo; f1hi = ds1 + hi;
+    ka_valid_shifts(P, 0, 1, ref_len, lo, hi); r0lo = top - ds0 + lo; r0hi = top - ds0 + hi;
+    ka_valid_shifts(P, 1, 1, ref_len, lo, hi); r1lo = top - ds1 + lo; r1hi = top - ds1 + hi;
+  }
+  const int o_min = max(0, min(min(f0lo, f1lo), min(r0lo, r1lo))), o_end = min(top + 1, max(max(f0hi, f1hi), max(r0hi, r1hi)));
+  const lds_u32_t *k0 = (const lds_u32_t *)(S.ka[0] + LDS_PAD), *k1 = (const lds_u32_t *)(S.ka[1] + LDS_PAD);
+  uint32_t todo = 0;  // bit i: the window at o_min + gl + 16 i is worth a fetch (at most 12 offsets a lane: reads up to 192 bases)
+  for (int i = 0, o = o_min + gl; i < 16 && o < o_end; i++, o += G) {
+    const int orv = top - o;
+    const uint32_t asked = (uint32_t)(o >= f0lo && o < f0hi) | ((uint32_t)(o >= f1lo && o < f1hi) << 1) |
+                           ((uint32_t)(o >= r0lo && o < r0hi) << 2) | ((uint32_t)(o >= r1lo && o < r1hi) << 3);
+    const uint32_t known = ((k0[o >> 4] >> (2 * (o & 15))) & 3u) | (((k1[orv >> 4] >> (2 * (orv & 15))) & 3u) << 2);
+    if (asked & ~known) todo |= 1u << i;
+  }
+  while (todo) {
+    uint4 tg[KA_M];
+    uint32_t meta[KA_M];  // fingerprint << 1 | the window is the reverse complement of its canonical form
+    int off[KA_M];
+#pragma unroll
+    for (int i = 0; i < KA_M; i++) {
+      off[i] = -1;
+      meta[i] = 0;
+      tg[i] = make_uint4(0, 0, 0, 0);
+      if (todo) {
+        const int o = o_min + gl + G * (__ffs((int)todo) - 1);
+        todo &= todo - 1;
+        bool swapped;
+        const uint64_t hc = sf::mix64(sf::canon(lds_window(sref, 2 * o) & kmask, wl, swapped));  // (the hash k_pres_insert files it under)
+        off[i] = o;
+        meta[i] = (sf::fp_of(hc) << 1) | (swapped ? 1u : 0u);
+        tg[i] = P.pres[sf::bucket_of(hc, P.pres_lgb)];
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < KA_M; i++) {
+      if (off[i] < 0) continue;
+      const uint32_t a = sf::to_window_frame(sf::absent_of(tg[i].x, tg[i].y, tg[i].z, tg[i].w, meta[i] >> 1), meta[i] & 1u);
+      const int o = off[i], orv = top - o;
+      if (a & 3u)
+        __hip_atomic_fetch_or((lds_u32_t *)(S.ka[0] + LDS_PAD) + (o >> 4), (a & 3u) << (2 * (o & 15)), __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_WAVEFRONT);
+      if (a >> 2)
+        __hip_atomic_fetch_or((lds_u32_t *)(S.ka[1] + LDS_PAD) + (orv >> 4), (a >> 2) << (2 * (orv & 15)), __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_WAVEFRONT);
+    }
+  }
+}
+
+template <int NQ, bool KA>
+__device__ __forceinline__ void search_ka(const DevParams &P, GLds<NQ, KA> &S, lds_u32_t *stage, int ref_len, int wide, int lone,
+                                          int lane, int gl, int &wcode, uint32_t &wrid) {
   lds_u32_t *s_best = (lds_u32_t *)&S.best;
   if (gl == 0) *s_best = (uint32_t)INF_CODE;
   wave_sync();
+  if (P.sf) {  // (lone: uniform over the chain's 16 lanes, not over the wavefront -- the sweep has no cross-lane step)
+    if (lone) sweep_ka<NQ, KA>(P, S, ref_len, gl);
+    wave_sync();  // ka
+  }
   const int wl = P.wl;
   uint32_t need = ka_need1<NQ, KA>(P, S, ref_len, gl) | (ka_need2<NQ, KA>(P, S, ref_len, gl, false) << 8);
   int best = INF_CODE;
@@ -1085,7 +1158,7 @@ __device__ __forceinline__ void search_mc(const DevParams &P, Chain *c, uint32_t
   PT(18);
   int wcode = INF_CODE, t0 = 0;
   uint32_t wrid = 0;
-  if constexpr (KA) search_ka<NQ, KA>(P, S, stage, ref_len, wide, lane, gl, wcode, wrid);
+  if constexpr (KA) search_ka<NQ, KA>(P, S, stage, ref_len, wide, h.prev_unmatched ? 1 : 0, lane, gl, wcode, wrid);
   else for (int ph = 0; ph < 6 && t0 < P.maxshift; ph++) {
     const int w = wide ? P.plan[1][ph] : P.plan[0][ph];
     if (w <= 0) break;

@@ -55,6 +55,7 @@ class ReorderOpts:
     known_absent: int = 0     # four-chain round kernel: chains remember known-absent windows (0 on, -1 off; same results)
     sort_prefix_bits: int = 0  # dictionary sort: bits of the key hash the radix sort orders, the rest by exact repair (0 = library's choice, 64 = full sort; same results)
     dict_build_mode: int = 0  # dictionary build: 0 = library's choice (keys from the unpack pass, table written in one pass), 1 = key pass + memset + merge + insert (same results)
+    strand_filter: int = 0    # four-chain round kernel: lone seeds sweep their windows through the strand-symmetric presence table (0 = library's choice, -1 off, n > 0 = on with at most 2^n buckets; same results)
 
     def to_c(self):
         o = _lib.Opts()
@@ -81,6 +82,7 @@ class ReorderOpts:
         o.known_absent = self.known_absent
         o.sort_prefix_bits = self.sort_prefix_bits
         o.dict_build_mode = self.dict_build_mode
+        o.strand_filter = self.strand_filter
         o.num_devices = len(self.devices)
         for i, d in enumerate(self.devices):
             o.devices[i] = d

@@ -3,6 +3,10 @@
  * synthetic 25x pool; per search it counts the tag fetches of (a) the round-5 plan (ordered batches of 4 + 8 + 16 shifts,
  * then one fetch per distinct window) and (b) the same search when windows whose absence the chain already knows are
  * skipped and the remaining ones are taken in priority order in batches of 16 / 32 / 64 / 64...
+ * and (c) the same with the strand-symmetric rule for a chain that is still its seed read alone: before the search, one
+ * fetch per ref offset o that a still-unknown code of either strand asks about settles the window at o of ref AND the
+ * window at R - wl - o of revref (its reverse complement), for both dictionaries (an ideal presence table: no full
+ * buckets, no fingerprint collisions); the search then runs as in (b) on what is left.
  * Build: gcc -O2 -o /tmp/ka_sim tools/ka_sim.c -Ioracle -Loracle -loracle_reorder -Wl,-rpath,$PWD/oracle
  */
 #include <stdint.h>
@@ -23,6 +27,8 @@ typedef struct {
   uint64_t ref[MAXW], revref[MAXW];
   int ref_len;
   uint8_t ka[2][512][2]; /* [strand][offset][dict] known absent */
+  uint8_t kb[2][512][2]; /* the same under rule (c) */
+  uint64_t n_lone, n_lone_fail, fb_lone, fc_lone, fb_lone_fail, fc_lone_fail, f_sym, f_sweep;
   int single;            /* contig is still its seed read alone */
   /* running search */
   int in_search, last_shift, last_rev, last_flag;
@@ -85,9 +91,29 @@ static void finish_search(sim_t *S) {
     if (hit) S->f_old_hit += f; else S->f_old_fail += f;
     S->hist_batches_old[nb < 7 ? nb : 7]++;
   }
-  /* ---- (b) known-absent windows skipped, compacted batches */
-  {
+  /* ---- (b) known-absent windows skipped, compacted batches; pass 1: (c) = the symmetric sweep first, then the same */
+  uint64_t fb = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    uint8_t (*ka)[512][2] = pass ? S->kb : S->ka;
     uint64_t f = 0;
+    if (pass && S->single) {
+      for (int o = 0; o + wl <= R; o++) {
+        const int orv = R - wl - o;
+        int want = 0;
+        for (int l = 0; l < 2; l++) {
+          const int shf = o - S->s[l], shr = S->s[l] - orv;
+          if (shf >= 0 && shf < ms && S->e[l] + shf < R && !ka[0][o][l]) want = 1;
+          if (shr >= 0 && shr < ms && S->e[l] < R + shr && S->s[l] > shr && !ka[1][orv][l]) want = 1;
+        }
+        if (!want) continue;
+        f++;
+        S->f_sweep++;
+        for (int l = 0; l < 2; l++) {
+          if (absent(S, 0, o, l)) ka[0][o][l] = 1;
+          if (absent(S, 1, orv, l)) ka[1][orv][l] = 1;
+        }
+      }
+    }
     int nb = 0, inb = 0, cap = 16, stop = 0;
     uint8_t fetched[2][512];
     memset(fetched, 0, sizeof(fetched));
@@ -97,7 +123,7 @@ static void finish_search(sim_t *S) {
           int valid = !rev ? (S->e[l] + sh < R) : (S->e[l] < R + sh && S->s[l] > sh);
           if (!valid) continue;
           const int o = rev ? S->s[l] - sh : S->s[l] + sh;
-          if (S->ka[rev][o][l]) continue;
+          if (ka[rev][o][l]) continue;
           if (fetched[rev][o]) { /* present in this dictionary by the tags seen: no second fetch (eval_probe walks) */ continue; }
           if (inb == cap) { /* batch full: was the winner in it? */
             nb++;
@@ -109,15 +135,24 @@ static void finish_search(sim_t *S) {
           inb++;
           fetched[rev][o] = 1;
           for (int ll = 0; ll < 2; ll++)
-            if (absent(S, rev, o, ll)) S->ka[rev][o][ll] = 1;
+            if (absent(S, rev, o, ll)) ka[rev][o][ll] = 1;
           if (hit && wsh == sh && wrev == rev) { /* winner reached: the rest of this batch is fetched too */ }
         }
     /* a hit stops after the batch that holds the winner: count the rest of that batch */
     if (hit && !stop) { /* winner was in the last (partial) batch: nothing to add in the ideal model */ }
     if (inb) nb++;
-    S->f_new += f;
-    if (hit) S->f_new_hit += f; else S->f_new_fail += f;
-    S->hist_batches_new[nb < 7 ? nb : 7]++;
+    if (!pass) {
+      fb = f;
+      S->f_new += f;
+      if (hit) S->f_new_hit += f; else S->f_new_fail += f;
+      S->hist_batches_new[nb < 7 ? nb : 7]++;
+    } else {
+      S->f_sym += f;
+      if (S->single) {
+        S->n_lone++; S->fb_lone += fb; S->fc_lone += f;
+        if (!hit) { S->n_lone_fail++; S->fb_lone_fail += fb; S->fc_lone_fail += f; }
+      }
+    }
   }
 }
 
@@ -137,16 +172,16 @@ static int h_update(void *u, uint32_t rid, int reset, int rev, int shift, const 
   const int had_search = S->in_search;
   finish_search(S);
   const int W = S->W, Ro = S->ref_len, Rn = ref_len;
+  for (int pass = 0; pass < 2; pass++) {
+  uint8_t (*ka)[512][2] = pass ? S->kb : S->ka;
   uint8_t nk[2][512][2];
   memset(nk, 0, sizeof(nk));
   if (reset) {
     if (rev && S->single && had_search) { /* left search of a lone seed: ref <-> revref */
-      memcpy(nk[0], S->ka[1], sizeof(nk[0]));
-      memcpy(nk[1], S->ka[0], sizeof(nk[1]));
+      memcpy(nk[0], ka[1], sizeof(nk[0]));
+      memcpy(nk[1], ka[0], sizeof(nk[1]));
     }
-    if (!rev) S->single = 1;
   } else {
-    S->single = 0;
     /* ref_new[i] = ref_old[i + so] for i < cpy (modulo argmax flips); fixed length: so = shift */
     int so, cpy;
     const int n = Rn; /* fixed-length pools only in this probe */
@@ -159,17 +194,19 @@ static int h_update(void *u, uint32_t rid, int reset, int rev, int shift, const 
     for (int o = 0; o + 32 <= Rn; o++) {
       int bad = 0;
       for (int q = o; q < o + 32; q++) bad |= chg[q];
-      if (bad) { S->inval++; continue; }
-      S->kept++;
+      if (bad) { if (!pass) S->inval++; continue; }
+      if (!pass) S->kept++;
       for (int l = 0; l < 2; l++) {
-        nk[0][o][l] = S->ka[0][o + so][l];
+        nk[0][o][l] = ka[0][o + so][l];
         /* reverse strand: window at j of revref_new = ref_new window at Rn - 32 - j; old: ref_old window at that + so = revref_old offset Ro - 32 - (Rn - 32 - j + so) */
         const int j = Rn - 32 - o, jo = Ro - 32 - (o + so);
-        if (jo >= 0 && jo < 512) nk[1][j][l] = S->ka[1][jo][l];
+        if (jo >= 0 && jo < 512) nk[1][j][l] = ka[1][jo][l];
       }
     }
   }
-  memcpy(S->ka, nk, sizeof(nk));
+  memcpy(ka, nk, sizeof(nk));
+  }
+  if (reset) { if (!rev) S->single = 1; } else S->single = 0;
   memcpy(S->ref, ref, 8 * W);
   memcpy(S->revref, revref, 8 * W);
   S->ref_len = Rn;
@@ -216,6 +253,12 @@ int main(int argc, char **argv) {
   printf("tag fetches per search: round-5 plan %.2f (hit %.2f, fail %.2f)   known-absent %.2f (hit %.2f, fail %.2f)\n",
          (double)S->f_old / S->n_search, (double)S->f_old_hit / S->n_hit, (double)S->f_old_fail / S->n_fail,
          (double)S->f_new / S->n_search, (double)S->f_new_hit / S->n_hit, (double)S->f_new_fail / S->n_fail);
+  printf("tag fetches per search with the strand-symmetric sweep for lone seeds: %.2f (of which sweep fetches %.2f)\n",
+         (double)S->f_sym / S->n_search, (double)S->f_sweep / S->n_search);
+  printf("lone-seed searches %llu (fail %llu): tag fetches per search known-absent %.2f -> symmetric %.2f; failing ones %.2f -> %.2f\n",
+         (unsigned long long)S->n_lone, (unsigned long long)S->n_lone_fail, (double)S->fb_lone / (S->n_lone + !S->n_lone),
+         (double)S->fc_lone / (S->n_lone + !S->n_lone), (double)S->fb_lone_fail / (S->n_lone_fail + !S->n_lone_fail),
+         (double)S->fc_lone_fail / (S->n_lone_fail + !S->n_lone_fail));
   printf("batches old:"); for (int i = 0; i < 8; i++) printf(" %llu", (unsigned long long)S->hist_batches_old[i]);
   printf("\nbatches new:"); for (int i = 0; i < 8; i++) printf(" %llu", (unsigned long long)S->hist_batches_new[i]);
   printf("\nwindows kept %.1f / invalidated %.1f per update\n", (double)S->kept / (S->n_hit + 1), (double)S->inval / (S->n_hit + 1));
