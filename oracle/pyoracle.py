@@ -444,6 +444,72 @@ def ref_qualid(files, order, num_reads, paired_end, num_reads_per_block, quality
         return out, left
 
 
+def ref_decompress_bin():
+    """oracle/_ref/ref_decompress: the real decompress_short (decompress.cpp whole, write_fastq_block without its gzip
+    branch) behind a command line, or None."""
+    path = os.path.join(_HERE, "_ref", "ref_decompress")
+    return path if os.path.exists(path) else None
+
+
+def ref_decompress(blocks, seq_pieces, num_reads, paired_end, preserve_order, num_reads_per_block, quality=None, ids=None,
+                   paired_id_code=0, paired_id_match=False, num_thr=1, unit_range=None):
+    """Runs the REAL decompress_short on raw inputs, compressed by the reference's own codecs first.
+      blocks      {stream name: [raw bytes of block 0, 1, ...]} (what ref_streams returns)
+      seq_pieces  [(2-bit packed bytes, tail text)] per encoder thread: read_seq.bin.<t> / .tail before BSC_compress
+      quality     None (preserve_quality off) or [lines of file 1, lines of file 2] in slot order
+      ids         None (preserve_id off: numbered ids) or [ids of file 1, ids of file 2] in slot order; with
+                  paired_id_match only file 1's are written
+      unit_range  (start_num, end_num), all units by default
+    The stream blocks and the packed consensus go through the real BSC_compress (ref_decompress pack), the quality and id
+    lines through the real reorder_compress_quality_id (libref_qualid.so, identity read_order.bin, which needs
+    num_reads >= 4; with a block size above the unit count it is given the unit count).  -> ([text of file 1, text of file 2], sorted names of every file left in the directory)."""
+    import tempfile
+    U = num_reads // 2 if paired_end else num_reads
+    B = int(num_reads_per_block)
+    a, b = (0, U) if unit_range is None else unit_range
+    nf = 2 if paired_end else 1
+    with tempfile.TemporaryDirectory() as d, tempfile.TemporaryDirectory() as o:
+        files = {}
+        for s, bl in blocks.items():
+            for k, data in enumerate(bl):
+                files["%s.%d" % (s, k)] = bytes(data)
+        for t, (packed, tail) in enumerate(seq_pieces):
+            files["read_seq.bin.%d" % t] = bytes(packed)
+            files["read_seq.bin.%d.tail" % t] = tail.encode() if isinstance(tail, str) else bytes(tail)
+        lines = {}
+        for m in range(nf):
+            if quality is not None:
+                lines["quality_%d" % (m + 1)] = quality[m]
+            if ids is not None and not (m == 1 and paired_id_match):
+                lines["id_%d" % (m + 1)] = ids[m]
+        for name, ls in lines.items():
+            assert len(ls) == U, name
+            files[name] = b"".join(x + b"\n" for x in ls)
+        for name, data in files.items():
+            with open(os.path.join(d, name), "wb") as f:
+                f.write(data)
+        if lines:
+            assert num_reads >= 4, "reorder_compress_quality_id needs num_reads >= 4"
+            with open(os.path.join(d, "read_order.bin"), "wb") as f:
+                f.write(np.arange(num_reads, dtype=np.uint32).tobytes())
+            # (one block either way: the writer allocates num_reads_per_block strings, which at 2^30 takes most of a minute)
+            rc = ref_qualid_lib().ref_q_write(d.encode(), num_reads, int(paired_end), min(B, U), 1, int(quality is not None),
+                                              int(ids is not None), int(paired_id_match))
+            assert rc == 0
+            os.remove(os.path.join(d, "read_order.bin"))
+        subprocess.run([ref_decompress_bin(), "pack", d], check=True)
+        outs = [os.path.join(o, "out_%d.fastq" % (m + 1)) for m in range(2)]
+        argv = [num_reads, int(paired_end), int(preserve_order), int(quality is not None), int(ids is not None),
+                int(paired_id_code), int(paired_id_match), B, len(seq_pieces), int(num_thr), int(a), int(b)]
+        subprocess.run([ref_decompress_bin(), "run", d] + outs + [str(x) for x in argv], check=True)
+        assert sorted(os.listdir(o)) == [os.path.basename(p) for p in outs[:nf]]
+        texts = []
+        for p in outs[:nf]:
+            with open(p, "rb") as f:
+                texts.append(f.read())
+        return texts, sorted(os.listdir(d))
+
+
 def limbs(L):
     return (2 * L - 1) // 64 + 1
 

@@ -6,9 +6,14 @@ functions the stage replaces, on lists of ids, reads and qualities.  No attempt 
   modify_id           util.cpp:255-267
   numbered ids, the start_num / end_num cut    decompress.cpp:373-378, :402-419
 
-The reference's functions are eight and twelve lines long and take std::string arrays; nothing runs them from here, so
-this model is pinned by inspection and by the round trips of tests/test_fastq_out_cpu.py and
-tests/test_gpu_fastq_out.py, which end at the bytes of the FASTQ that went in."""
+Pinned by the reference's own code: tests/test_models_vs_ref_decompress.py runs the real decompress_short
+(oracle/_ref/ref_decompress: decompress.cpp whole, write_fastq_block without its gzip branch) on reference-written blocks
+and compares the files it writes byte for byte with assemble() -- numbered ids across a digit change and block edges,
+modify_id with codes 1, 2 and 3 (the first of two spaces, a one-character id), id_2 read without a match, ranges inside
+a block, on block edges, across steps and to the last unit at one and three blocks per step, two-line records, block
+windows.  One divergence is kept there: the reference writes a stale quality line behind an empty read that ends a
+block (bsc_str_array.cpp:149-162); this model writes the empty line.  The round trips of tests/test_fastq_out_cpu.py and
+tests/test_gpu_fastq_out.py end at the bytes of the FASTQ that went in."""
 import numpy as np
 
 

@@ -1,6 +1,8 @@
 """Hand-built inputs for the pins against the reference's own writers (test infrastructure, not product): encoder
 images for reorder_compress_streams with the edges named in tests/test_models_vs_ref.py, and FASTQ line images for
 reorder_compress_quality_id.  Everything is built here in Python; nothing is read from the reference."""
+import functools
+
 import numpy as np
 
 import decode_cases as dc
@@ -265,3 +267,108 @@ def load_qualid_fixture(case):
                                        max_len=int(ln.max()) if len(ln) else 0)
     return dict(files={name: z[name].tobytes() for name in names}, order=z["order"], N=int(z["num_reads"]), pe=pe,
                 B=int(z["num_reads_per_block"]), want=want)
+
+
+# ---------------------------------------------------------------- the real decompressor (oracle/_ref/ref_decompress)
+def pe_singleton_open():
+    """Blocks whose first read 1 is unaligned and whose later read 1s are too (decompress.cpp:240-250 never reads a u64
+    for read 1 there): at B = 3 the flags 4 2 4 | 0 1 3 | 2 4 2 | 1; read 2 of the flag-4 units aligned, so read_pos.bin
+    of such a block holds read 2 positions only."""
+    a = lambda p, rc="d", L=24, noise=((1, 1),): A(p, rc, L, noise)  # noqa: E731
+    us = [
+        (U(_bases(24, 31)), a(3000, "r")), (U("N"), U(_bases(9, 32))), (U(_bases(511, 33)), a(90000, "d", 511, ((0, 3), (510, 0)))),
+        (a(500, "d"), a(520, "r", 24, ())), (a(70000, "r", 24, full_noise(24, 34)), a(170000, "d")), (a(70010, "d", 0, ()), U(_bases(24, 35))),
+        (U(""), U("")), (U(_bases(30, 36)), a(7, "d", 1, ((0, 2),))), (U("ACGTN"), U("NNNN")),
+        (a(12, "r"), a(300000, "r", 24, ((23, 1),))),
+    ]
+    return units(us)
+
+
+@functools.lru_cache(maxsize=8)
+def seq_pieces(seq, T):
+    """The consensus text cut into T encoder threads -> [(2-bit packed bytes, tail text)]: read_seq.bin.<t> / .tail as
+    pack_compress_seq leaves them before BSC_compress (encoder.cpp:111-156; test_unpack_seq_format pins the format)."""
+    from test_gpu_decode import pack_seq
+    lens, pk, tl = pack_seq(seq, T)
+    cut = np.concatenate([[0], np.cumsum(lens // 4)]).astype(int)
+    return [(pk[cut[t]:cut[t + 1]], tl[t]) for t in range(T)]
+
+
+def quality_for(reads, mate=0):
+    """A quality line per read, of the read's length (BSC_str_array_decompress takes the lengths from read_lengths.bin):
+    windows of the repeated alphabet 33..126, so that a fixture holding them stays small."""
+    rep = QUAL_ALPHABET * 7
+    return [rep[(7 * i + 13 * mate) % 94:][:len(r)] for i, r in enumerate(reads)]
+
+
+TWO_SPACES = (lambda i: b"@M:%d 1:N:0 1" % i, lambda i: b"@M:%d 2:N:0 1" % i, 3)   # modify_id: the FIRST space counts
+
+
+def ids_for(form, n, mate=0):
+    f = TWO_SPACES if form == "two_spaces" else ID_FORMS[form]
+    return [f[mate](i) for i in range(n)]
+
+
+def consumed_blocks(units_, B, num_thr, a, b):
+    """The blocks decompress_short opens for the range [a, b) (decompress.cpp:122-138, :402-423): it starts with the
+    block that holds unit a, takes num_thr blocks per step, and stops after the step that reaches unit b."""
+    first = a // B
+    done, blk, out = first * B, first, []
+    per_step = min(num_thr * B, units_)
+    while True:
+        cur = min(per_step, units_ - done)
+        if cur == 0:
+            break
+        out += [blk + t for t in range(num_thr) if t * B < cur]
+        if done + cur >= b:
+            break
+        done += cur
+        blk += num_thr
+    return out
+
+
+# case -> (slots, paired_end, preserve_order, B, encoder threads, id source, quality, ((start, end, num_thr), ...))
+# id source: a form of ID_FORMS read from both files; (form, code) = paired_id_match, file 2's ids by modify_id; None =
+# preserve_id off, numbered ids.  Recorded by tests/golden/make_ref_golden.py as ref_decomp_<case>.npz.  Block sizes,
+# quality and thread counts are chosen so that no record shows the reference's stale quality line behind an empty read
+# at the end of a block (the kept divergence of tests/test_models_vs_ref_decompress.py); the maker asserts it.
+DECOMP_FIXTURES = {
+    "se_deltas_B3": (se_deltas, False, False, 3, 3, "srr", True, ((0, 11, 1), (4, 9, 1), (0, 11, 3))),
+    "pe_flags_po_noqual_B3_code3": (pe_flags, True, True, 3, 1, ("two_spaces", 3), False, ((0, 10, 3), (2, 10, 3), (5, 6, 1))),
+    "pe_singleton_numbered_B3": (pe_singleton_open, True, False, 3, 2, None, True, ((0, 10, 3), (5, 10, 3), (8, 10, 1))),
+    "se_mixed_po_noqual_B4": (se_mixed, False, True, 4, 1, "r", False, ((0, 11, 3), (3, 4, 1), (4, 8, 1))),
+    "pe_pairdist_B4_code1": (pe_pairdist, True, False, 4, 3, ("srr", 1), True, ((0, 9, 1), (3, 9, 3))),
+    "pe_corner_po_B3_code2": (lambda: units(_pe_corner()), True, True, 3, 1, ("r", 2), True, ((0, 8, 1), (1, 7, 3))),
+    "pe_pairdist_po_B4_id2": (pe_pairdist, True, True, 4, 1, "illumina", True, ((0, 9, 3), (4, 8, 1))),
+}
+
+
+def decomp_fixture_inputs(case):
+    """-> dict(enc, seq, N, reads, pe, preserve_order, B, T, ids = [file 1, file 2] or None, quality = [...] or None,
+    code = paired id code or None, ranges)."""
+    make, pe, preserve_order, B, T, idsrc, quality, ranges = DECOMP_FIXTURES[case]
+    seq = consensus()
+    enc, N, reads = make_enc(make(), seq, shuffle=pe or preserve_order)
+    n = N // 2 if pe else N
+    nf = 2 if pe else 1
+    form, code = idsrc if isinstance(idsrc, tuple) else (idsrc, None)
+    ids = None if form is None else [ids_for(form, n, m) for m in range(nf)]
+    quals = [quality_for(reads[m * n:(m + 1) * n], m) for m in range(nf)] if quality else None
+    return dict(enc=enc, seq=seq, N=N, reads=reads, pe=pe, preserve_order=preserve_order, B=B, T=T, ids=ids, quality=quals,
+                code=code, ranges=ranges)
+
+
+def load_decomp_fixture(case):
+    """-> dict(seq, N, pe, preserve_order, B, streams = {name: (bytes, block offsets)}, ids / quality = [lines of file 1,
+    of file 2] or None, code, ranges, text = {(start, end, num_thr): [file 1's text, file 2's]}), all from the file."""
+    z = np.load(os.path.join(GOLDEN, "ref_decomp_%s.npz" % case))
+    pe = bool(z["paired_end"])
+    nf = 2 if pe else 1
+    lines = lambda k: z[k].tobytes().split(b"\n")[:-1]  # noqa: E731
+    ranges = [tuple(int(x) for x in r) for r in z["ranges"]]
+    return dict(seq=z["seq"].tobytes().decode(), N=int(z["num_reads"]), pe=pe, preserve_order=bool(z["preserve_order"]),
+                B=int(z["num_reads_per_block"]), streams={s: (z[s].tobytes(), z[s + ".off"]) for s in sm.stream_names(pe)},
+                ids=[lines("id_%d" % (m + 1)) for m in range(nf)] if "id_1" in z else None,
+                quality=[lines("quality_%d" % (m + 1)) for m in range(nf)] if "quality_1" in z else None,
+                code=int(z["paired_id_code"]) or None, ranges=ranges,
+                text={r: [z["text_%d.%d" % (m + 1, k)].tobytes() for m in range(nf)] for k, r in enumerate(ranges)})

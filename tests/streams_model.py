@@ -1,7 +1,8 @@
 """Checker for the per-block read streams (test infrastructure, not product).
 
 write_streams  vectorised numpy restatement of the writer, reference src/reorder_compress_streams.cpp:76-362
-read_block     restatement of the decompressor's reader of one block, reference src/decompress.cpp:223-321
+read_block     restatement of the decompressor's reader of one block, reference src/decompress.cpp:223-321; pinned by
+               the real decompress_short on blocks the real writer wrote (tests/test_models_vs_ref_decompress.py)
 
 Stream names are the reference's file names (reorder_compress_streams.cpp:34-74).
 """
@@ -190,7 +191,11 @@ _RC = str.maketrans("ACGTN", "TGCAN")
 
 def read_block(blk, seq, num_units, paired_end, preserve_order):
     """decompress.cpp:223-321 for one block: blk = {stream name: bytes}, seq = consensus text.
-    -> list of reads of the block's units (single-end) or of (read 1, read 2) tuples (paired-end)."""
+    -> list of reads of the block's units (single-end) or of (read 1, read 2) tuples (paired-end).
+    Compared with the reads the real decompress_short restores from the same blocks in
+    tests/test_models_vs_ref_decompress.py.  The final assertion (every stream consumed exactly) is this reader's refusal
+    of a block the reference cannot read either: without preserve_order, one that opens with an unaligned read 1 and holds
+    an aligned read 1 later (the writer stores a u16 delta there, this reader takes a u64)."""
     flag = blk["read_flag.txt"].decode()
     lens = np.frombuffer(blk["read_lengths.bin"], np.uint16)
     posb, rcs, un = blk["read_pos.bin"], blk["read_rev.txt"].decode(), blk["read_unaligned.txt"].decode()

@@ -260,7 +260,7 @@ def chain(request):
                     q.set_order_from_encoder(enc, N, pe)
                 q.from_fastq(f[m], num_reads_per_block=B_CHAIN)
             yield types.SimpleNamespace(case=case, f=f, pe=pe, N=N, order=None if keep_order else order, ds=ds, qs=qs,
-                                        U=N // 2 if pe else N)
+                                        U=N // 2 if pe else N, keep_order=keep_order, enc=enc, ss=ss)
 
 
 def test_sources_in_hbm_equal_sources_from_the_host(chain):
@@ -322,6 +322,48 @@ def test_round_trip_to_the_users_file(chain):
             assert fo.download()[0] == text
             fo.assemble(c.ds, c.N, ids=c.qs[0], paired_end=True, num_reads_per_block=B_CHAIN, mate=1, paired_id_code=2)
             assert fo.download()[0] == fm.assemble(by_slot[0], by_slot[1])[0].replace(b"/2\n", b"/1\n")
+
+
+@pytest.mark.skipif(po.ref_decompress_bin() is None or po.ref_qualid_lib() is None,
+                    reason="oracle/_ref/ref_decompress not built (needs the reference sources)")
+def test_reference_decompressor_reads_what_the_gpu_wrote(chain):
+    """The GPU's own stream blocks, packed consensus and quality / id blocks go to files, through the reference's codecs
+    (BSC_compress, reorder_compress_quality_id), and the REAL decompress_short (oracle/_ref/ref_decompress, a CPU child
+    process) reads them: the file or files it writes are the text FastqOutStage assembled, and with preserve_order the
+    file that went in.  For the pair also with paired_id_match (id_2 not written) over a range."""
+    import streams_model as sm
+    from spring_amd import FastqOutStage
+    c = chain
+    nf = len(c.f)
+    blocks = {s: c.ss.blocks(s) for s in sm.stream_names(c.pe)}
+    lens = c.enc.streams()["seq_len_tid"]
+    packed, tails = c.enc.seq_packed()
+    cut = np.concatenate([[0], np.cumsum(lens // np.uint64(4))]).astype(int)
+    pieces = [(packed[cut[t]:cut[t + 1]], tails[t]) for t in range(len(tails))]
+    assert len(pieces) == 2 and cut[-1] == len(packed)
+    quals = [[x for blk in c.qs[m].blocks(qm.QUALITY) for x in blk] for m in range(nf)]
+    ids = [[x for blk in c.qs[m].blocks(qm.ID) for x in blk] for m in range(nf)]
+    with FastqOutStage() as fo:
+        gpu = []
+        for m in range(nf):
+            fo.assemble(c.ds, c.N, quality=c.qs[m], ids=c.qs[m], paired_end=c.pe, num_reads_per_block=B_CHAIN, mate=m)
+            gpu.append(fo.download()[0])
+        texts, left = po.ref_decompress(blocks, pieces, c.N, c.pe, c.keep_order, B_CHAIN, quality=quals, ids=ids, num_thr=3)
+        assert left == [] and len(texts) == nf
+        for m in range(nf):
+            assert texts[m] == gpu[m], (c.case, m)
+            if c.keep_order:
+                assert texts[m] == c.f[m]
+        if c.pe:
+            a, b = B_CHAIN - 3, c.U - 1   # starts inside block 0, ends inside the last block
+            assert 0 < a < B_CHAIN < b < c.U
+            texts, left = po.ref_decompress(blocks, pieces, c.N, True, c.keep_order, B_CHAIN, quality=quals, ids=ids,
+                                            paired_id_code=1, paired_id_match=True, num_thr=1, unit_range=(a, b))
+            assert left == []   # both blocks opened; id_2.<b> was never there, so file 2's ids can only be modify_id's
+            for m in range(2):
+                fo.assemble(c.ds, c.N, quality=c.qs[m], ids=c.qs[0], paired_end=True, num_reads_per_block=B_CHAIN, mate=m,
+                            paired_id_code=1 if m else None, unit_range=(a, b))
+                assert texts[m] == fo.download()[0], (c.case, m, "paired_id_match")
 
 
 # ---------------------------------------------------------------- refusals
