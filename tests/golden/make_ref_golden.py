@@ -20,7 +20,8 @@ ref_stage_<case>.npz     the cases of tests/ref_stage_cases.py through the refer
                          files uncompressed; for thr3 the hand-made three-thread set instead, `reorder_by_reference` =
                          False), `unmatched` = the number it printed, `encoder/<file>` = every file encoder_main<N> left
                          on that set (read_seq.bin.<t>.raw = the .bsc inflated by the real BSC_decompress), `matched` =
-                         the two numbers it printed.
+                         the two numbers it printed.  fixed33 / fixed150 / fixed251 are recorded for a
+                         reverse-complemented record in temp.dna.0 (asserted when they are written).
 ref_decomp_<case>.npz    the cases of tests/ref_cases.py::DECOMP_FIXTURES through the reference's writers and then its real
                          decompressor (ref_decompress = decompress_short whole): the consensus `seq`, num_reads /
                          paired_end / preserve_order / num_reads_per_block / paired_id_code (0 = no paired_id_match), per
@@ -135,6 +136,8 @@ if only not in (None, "stage"):
     sys.exit(0)
 for case in sc.FIXTURES:
     out = sc.record_fixture(case)
+    if case in sc.R_RECORD_CASES:   # what the case is recorded for: a reverse-complemented record in temp.dna.0
+        assert sc.holds_r_record({k[len("reorder/"):]: v.tobytes() for k, v in out.items() if k.startswith("reorder/")}, int(out["L"])), case
     path = os.path.join(HERE, "ref_stage_%s.npz" % case)
     np.savez_compressed(path, **out)
     print(case, int(out["n"]), os.path.getsize(path))

@@ -66,7 +66,18 @@ def n_reads_for(read, ln, n, nN, deep, seed):
 # ------------------------------------------------------------------ the recorded fixtures
 # case -> (what it carries).  Sizes are the smallest at which the edge still occurs and the .npz stays below the
 # largest fixture of tests/golden (the inputs are random bases: they do not compress, and temp.dna.* holds them again).
-FIXTURES = ("fixed100", "var", "short20", "long300", "deepN", "thr3")
+FIXTURES = ("fixed100", "var", "short20", "long300", "deepN", "thr3", "fixed33", "fixed150", "fixed251")
+# One read length that is no multiple of four, residues 1, 2 and 3: the fixed-length temp.dna writer takes a
+# reverse-complemented record's bytes across a limb boundary and masks the last, partial byte only there.  case -> (seed,
+# L, n): reads of a genome of 5 L bases at 1 % substitutions, n the smallest at which the reference's -t 1 run leaves two
+# contigs and temp.dna.0 holds a reverse-complemented record.
+R_RECORD_CASES = {"fixed33": (206, 33, 9), "fixed150": (207, 150, 9), "fixed251": (208, 251, 12)}
+
+
+def holds_r_record(reorder_files, L):
+    """temp.dna.0 of a one-thread file set of one read length holds a record written reverse-complemented."""
+    rev = reorder_files["read_rev.txt.0"]
+    return b"r" in rev and len(reorder_files["temp.dna.0"]) == len(rev) * (2 + (L + 3) // 4)
 
 
 def fixture_inputs(case):
@@ -90,6 +101,9 @@ def fixture_inputs(case):
     elif case == "thr3":
         dna, n, L = three_thread_set(240, 1600, 24)
         T, K, nN = 3, 6, 0
+    elif case in R_RECORD_CASES:   # 11-byte records; the workload's length; 8 limbs
+        rseed, L, n = R_RECORD_CASES[case]
+        dna, nN = rs.pack_fixed(rs.np_reads(rseed, 5 * L, n, L, 0.01)), 4
     else:
         raise KeyError(case)
     read, ln = po.load_dna(dna, n, L)

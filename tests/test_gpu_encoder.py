@@ -3,8 +3,8 @@ oracle/encoder_oracle.c on identical inputs.  Bar: every output stream bit-exact
 import numpy as np
 import pytest
 
-from helpers import (decode_reads, interleave_order_N, make_N_reads, named_set, read_strings, same_encoding,
-                     unpack_dnaN)
+from helpers import (decode_reads, interleave_order_N, make_N_reads, named_set, read_strings, reorder_file_set,
+                     same_encoding, unpack_dnaN)
 from oracle import pyoracle as po
 
 pytestmark = pytest.mark.gpu
@@ -243,17 +243,19 @@ def test_fastq_to_encoder_streams_end_to_end(paired):
 
 
 @pytest.mark.parametrize("recompress", [False, True])
-def test_encoder_run_file_contract_after_reorder_run(tmp_path, recompress):
+@pytest.mark.parametrize("name", ["var2k", "syn5k_150"])
+def test_encoder_run_file_contract_after_reorder_run(tmp_path, name, recompress):
     """spring_encoder_run as a drop-in for call_encoder: it consumes the per-tid files a reorder stage left in
     temp_dir (here spring_reorder_run's; with recompress=True the gzip members are rewritten with real deflate
-    blocks, as boost::iostreams::gzip_compressor produces them) and leaves encoder_main's files."""
+    blocks, as boost::iostreams::gzip_compressor produces them) and leaves encoder_main's files.  var2k: records of
+    varying size; syn5k_150: the fixed-size, already-oriented temp.dna records of a pool of one read length, L % 4 = 2."""
     import ctypes as C
     import gzip
     import os
 
     import spring_amd
     from spring_amd import _lib
-    name, T, K = "var2k", 3, 12
+    T, K = 3, 12
     dna, n, L = named_set(name)
     read, ln = po.load_dna(dna, n, L)
     Nreads = make_N_reads(read_strings(read, ln), 250, 8)
@@ -266,6 +268,10 @@ def test_encoder_run_file_contract_after_reorder_run(tmp_path, recompress):
     L_ = _lib.lib()
     o = spring_amd.ReorderOpts(num_chains=K, num_thr=T).to_c()
     assert L_.spring_reorder_run(d.encode(), L, T, 0, n, 0, C.byref(o)) == 0, L_.spring_reorder_last_error()
+    streams = po.reorder_rounds(read, ln, L, K, T)
+    for f, data in reorder_file_set(read, ln, L, streams).items():   # what the encoder is about to read, padding bits included
+        if f.startswith("temp.dna"):
+            assert open(os.path.join(d, f), "rb").read() == data, f
     if recompress:
         for t in range(T):
             for f in ("read_rev.txt", "tempflag.txt", "temppos.txt", "read_lengths.bin"):
@@ -275,7 +281,7 @@ def test_encoder_run_file_contract_after_reorder_run(tmp_path, recompress):
     info = _lib.EncoderInfo()
     rc = L_.spring_encoder_run(d.encode(), L, T, n + len(Nreads), n, -1, C.byref(info))
     assert rc == 0, L_.spring_reorder_last_error()
-    want = po.encode(read, ln, L, po.reorder_rounds(read, ln, L, K, T), num_thr=T, dnaN=dnaN, order_N=order_N)
+    want = po.encode(read, ln, L, streams, num_thr=T, dnaN=dnaN, order_N=order_N)
     rd = lambda f: open(os.path.join(d, f), "rb").read()  # noqa: E731
     assert rd("read_pos.bin") == want["pos"].tobytes()
     assert rd("read_noise.txt") == want["noise"]

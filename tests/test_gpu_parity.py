@@ -838,6 +838,39 @@ def test_call_reorder_two_chain_groups(tmp_path):
     _check_file_set(_read_file_set(tmp_path, T), want, read, ln, L, T)
 
 
+@pytest.mark.parametrize("devices", [(), (0, 0)])
+@pytest.mark.parametrize("L", [150, 153])
+def test_call_reorder_file_set_at_lengths_not_a_multiple_of_four(tmp_path, L, devices):
+    """The drop-in's temp.dna.<tid> / temp.dna.singleton where the fixed-length writer takes a reverse-complemented
+    record's bytes across a limb boundary and masks the last, partial byte (L % 4 = 2: the workload's 150, whose 40-byte
+    records never straddle an output word; L % 4 = 1: 153, whose 41-byte records do), on one device and on a device list."""
+    sa = _sa()
+    from spring_amd.reorder import CompressionParams
+    n, K, T = 50_000, 256, 5
+    dna = sa.synth_dna_host(n, L, n * L // 25, 31, 10000)
+    (tmp_path / "input_clean_1.dna").write_bytes(dna)
+    sa.call_reorder(str(tmp_path), CompressionParams(L, [n, 0], num_thr=T), sa.ReorderOpts(num_chains=K, num_thr=T, devices=devices))
+    read, ln = po.load_dna(dna, n, L)
+    want = po.reorder_rounds(read, ln, L, K, T)
+    assert np.count_nonzero(want["rc"] == ord("r")) > 0 and np.count_nonzero(want["rc"] == ord("d")) > 0
+    _check_file_set(_read_file_set(tmp_path, T), want, read, ln, L, T)
+
+
+def test_call_reorder_two_chain_groups_150bp(tmp_path):
+    """... and with the chains in two groups at the workload's length: a tid's temp.dna stream is written in two pieces, split
+    at `records of the first group * record size` bytes."""
+    sa = _sa()
+    from spring_amd.reorder import CompressionParams
+    n, L, K, T = 200_000, 150, 4096, 5
+    dna = sa.synth_dna_host(n, L, n * L // 25, 31, 10000)
+    (tmp_path / "input_clean_1.dna").write_bytes(dna)
+    sa.call_reorder(str(tmp_path), CompressionParams(L, [n, 0], num_thr=T), sa.ReorderOpts(num_chains=K, num_thr=T, phases=2))
+    read, ln = po.load_dna(dna, n, L)
+    want = po.reorder_rounds_ph(read, ln, L, K, T)
+    assert np.count_nonzero(want["rc"] == ord("r")) > 0
+    _check_file_set(_read_file_set(tmp_path, T), want, read, ln, L, T)
+
+
 def test_call_reorder_lengths_that_hide_in_a_fixed_size_stream(tmp_path):
     """Reads of 97..100 bases all take 2 + 25 bytes: the stream has the size of a fixed-length one, the device-side
     length check notices, and the stage falls back to walking the records."""

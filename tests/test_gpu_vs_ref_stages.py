@@ -21,7 +21,7 @@ from ref_stage_cases import fixture_files
 
 pytestmark = pytest.mark.gpu
 
-CASES = ("fixed100", "var", "short20", "long300", "deepN")     # (thr3: see above)
+CASES = ("fixed100", "var", "short20", "long300", "deepN", "fixed33", "fixed150", "fixed251")     # (thr3: see above)
 
 
 def _fx(case):

@@ -212,6 +212,11 @@ def test_stage_fixture_holds_its_case_and_equals_the_oracle(case):
         assert depth > 1000 and 1000 <= want["matched_N"] < len(inp["order_N"])
     elif case == "thr3":
         assert tuple(z["matched"].tolist()) == (0, 0) and np.count_nonzero(want["seq_len_tid"]) == 3
+    elif case in sc.R_RECORD_CASES:   # one read length, no multiple of four, and a reverse-complemented record in temp.dna.0
+        assert L == sc.R_RECORD_CASES[case][1] and L % 4 != 0 and np.all(ln == L)
+        assert sc.holds_r_record(rfiles, L) and b"d" in rfiles["read_rev.txt.0"]
+    else:
+        raise KeyError(case)
 
 
 @needs_ref
