@@ -114,7 +114,7 @@ int spring_fastq_out_assemble(spring_fastq_out_ctx *ctx, const spring_fastq_out_
 
 /* text: info.bytes bytes; rec_off: info.num_units + 1 offsets into text.  Either may be NULL. */
 int spring_fastq_out_download(spring_fastq_out_ctx *ctx, uint8_t *text, uint64_t *rec_off);
-/* The text to a plain file through a ring of pinned staging chunks (gzip output stays with the caller).  append = 0
+/* The text to a plain file through a ring of pinned staging chunks (gzip output: include/spring_gzip.h).  append = 0
  * truncates.  A file that cannot be opened or written gives SPRING_REORDER_E_IO. */
 int spring_fastq_out_write(spring_fastq_out_ctx *ctx, const char *path, int32_t append, spring_fastq_out_info *info);
 

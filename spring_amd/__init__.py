@@ -9,3 +9,4 @@ from .streams import StreamsStage, call_reorder_compress_streams  # noqa: F401,E
 from .decode import DecodeStage  # noqa: F401,E402
 from .qualid import QualIdStage  # noqa: F401,E402
 from .fastq_out import FastqOutStage  # noqa: F401,E402
+from .gzip import GzipStage  # noqa: F401,E402

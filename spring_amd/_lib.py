@@ -51,6 +51,12 @@ FASTQ_OUT_EXPORTS = [
     "spring_fastq_out_write", "spring_fastq_out_get_info",
 ]
 
+# include/spring_gzip.h: a list of its own as well
+GZIP_EXPORTS = [
+    "spring_gzip_create", "spring_gzip_destroy", "spring_gzip_set_chunk_bytes", "spring_gzip_from_fastq_out",
+    "spring_gzip_from_host", "spring_gzip_download", "spring_gzip_write", "spring_gzip_get_info",
+]
+
 
 class Opts(C.Structure):
     _fields_ = [("device", C.c_int32), ("num_chains", C.c_uint32), ("num_thr", C.c_int32),
@@ -129,6 +135,19 @@ class FastqOutInfo(C.Structure):
 
     def asdict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class GzipInfo(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("num_members", "bytes_in", "bytes_out", "chunk_bytes", "num_chunks",
+                                           "chunks_stored")]
+                + [("ms_device", C.c_double), ("ms_file", C.c_double), ("ms_pass", C.c_double * 6)])
+
+    def asdict(self):
+        d = {}
+        for k, _ in self._fields_:
+            v = getattr(self, k)
+            d[k] = list(v) if hasattr(v, "__len__") else v
+        return d
 
 
 class DecodeInfo(C.Structure):
@@ -293,6 +312,18 @@ def lib():
     L.spring_fastq_out_download.argtypes = [vp, u8p, vp]
     L.spring_fastq_out_write.argtypes = [vp, C.c_char_p, C.c_int32, C.POINTER(FastqOutInfo)]
     L.spring_fastq_out_get_info.argtypes = [vp, C.POINTER(FastqOutInfo)]
+    L.spring_gzip_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.spring_gzip_destroy.argtypes = [vp]
+    L.spring_gzip_destroy.restype = None
+    L.spring_gzip_set_chunk_bytes.argtypes = [vp, C.c_uint32]
+    L.spring_gzip_from_fastq_out.argtypes = [vp, vp, C.c_uint64, C.c_int32, C.POINTER(GzipInfo)]
+    L.spring_gzip_from_host.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint64, C.c_int32, C.POINTER(GzipInfo)]
+    L.spring_gzip_download.argtypes = [vp, u8p, vp]
+    L.spring_gzip_write.argtypes = [vp, C.c_char_p, C.c_int32, C.POINTER(GzipInfo)]
+    L.spring_gzip_get_info.argtypes = [vp, C.POINTER(GzipInfo)]
+    for name in GZIP_EXPORTS:
+        if name != "spring_gzip_destroy":
+            getattr(L, name).restype = C.c_int
     for name in FASTQ_OUT_EXPORTS:
         if name != "spring_fastq_out_destroy":
             getattr(L, name).restype = C.c_int

@@ -589,6 +589,16 @@ int assemble(spring_fastq_out_ctx *ctx, const spring_fastq_out_params &P, const 
 
 }  // namespace
 
+int sr::fastq_out_view(spring_fastq_out_ctx *ctx, FastqOutView *v) {
+  if (!ctx || !v) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  if (!ctx->have) return fail(SPRING_REORDER_E_STATE, "no text assembled yet");
+  v->dev = ctx->dev;
+  v->info = ctx->info;
+  v->text = ctx->text.as<uint8_t>();
+  v->rec_off = ctx->rec_off.as<uint64_t>();
+  return 0;
+}
+
 extern "C" {
 
 int spring_fastq_out_create(int device, spring_fastq_out_ctx **out) {

@@ -1,12 +1,14 @@
 // spring_amd/csrc/fastq_out_internal.h -- what the FASTQ assembler (fastq_out.hip) reads in place from a decode
 // context (decode.hip) and from a quality / id context (qualid.hip): the device buffers of their last result, with the
-// sizes that bound them.  Internal to the library.
+// sizes that bound them; and what the gzip stage (gzip.hip) reads in place from the assembler's own context.  Internal
+// to the library.
 #ifndef SPRING_FASTQ_OUT_INTERNAL_H_
 #define SPRING_FASTQ_OUT_INTERNAL_H_
 
 #include <stdint.h>
 
 #include "spring_decode.h"
+#include "spring_fastq_out.h"
 #include "spring_qualid.h"
 
 namespace sr {
@@ -29,6 +31,14 @@ struct QualIdView {
   const uint64_t *table[2];       // host: num_blocks + 1 block offsets
 };
 int qualid_view(spring_qualid_ctx *ctx, QualIdView *v);   // fails unless the context holds a result
+
+struct FastqOutView {
+  int dev;
+  spring_fastq_out_info info;     // num_units, bytes
+  const uint8_t *text;            // device: info.bytes bytes from a 16-byte-aligned start, 16 bytes of padding behind them
+  const uint64_t *rec_off;        // device: num_units + 1 offsets into text
+};
+int fastq_out_view(spring_fastq_out_ctx *ctx, FastqOutView *v);   // fails unless the context holds a text
 
 }  // namespace sr
 #endif

@@ -125,7 +125,7 @@ class FastqOutStage:
         return buf[:n]
 
     def write(self, path, append=False):
-        """The text to a plain file (gzip output stays with the caller); -> info with ms_file."""
+        """The text to a plain file (gzip output: GzipStage.compress(this stage)); -> info with ms_file."""
         info = _lib.FastqOutInfo()
         _chk(self._L.spring_fastq_out_write(self._h, str(path).encode(), int(append), C.byref(info)))
         self.info = info.asdict()
