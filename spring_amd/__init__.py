@@ -10,3 +10,4 @@ from .decode import DecodeStage  # noqa: F401,E402
 from .qualid import QualIdStage  # noqa: F401,E402
 from .fastq_out import FastqOutStage  # noqa: F401,E402
 from .gzip import GzipStage  # noqa: F401,E402
+from .bwt import BwtStage  # noqa: F401,E402

@@ -57,6 +57,14 @@ GZIP_EXPORTS = [
     "spring_gzip_from_host", "spring_gzip_download", "spring_gzip_write", "spring_gzip_get_info",
 ]
 
+# include/spring_bwt.h: a list of its own as well
+BWT_EXPORTS = [
+    "spring_bwt_create", "spring_bwt_destroy", "spring_bwt_set_block_bytes", "spring_bwt_set_workspace_bytes",
+    "spring_bwt_workspace_need", "spring_bwt_from_host", "spring_bwt_from_streams", "spring_bwt_download",
+    "spring_bwt_segments", "spring_bwt_get_info", "spring_bwt_encode_inplace",
+]
+BWT_MAX_INDEXES = 256  # SPRING_BWT_MAX_INDEXES
+
 
 class Opts(C.Structure):
     _fields_ = [("device", C.c_int32), ("num_chains", C.c_uint32), ("num_thr", C.c_int32),
@@ -141,6 +149,19 @@ class GzipInfo(C.Structure):
     _fields_ = ([(k, C.c_uint64) for k in ("num_members", "bytes_in", "bytes_out", "chunk_bytes", "num_chunks",
                                            "chunks_stored")]
                 + [("ms_device", C.c_double), ("ms_file", C.c_double), ("ms_pass", C.c_double * 6)])
+
+    def asdict(self):
+        d = {}
+        for k, _ in self._fields_:
+            v = getattr(self, k)
+            d[k] = list(v) if hasattr(v, "__len__") else v
+        return d
+
+
+class BwtInfo(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("num_segments", "bytes", "max_segment", "sub_batches", "rounds",
+                                           "rounds_total", "workspace_bytes")]
+                + [("ms_device", C.c_double), ("ms_pass", C.c_double * 5)])
 
     def asdict(self):
         d = {}
@@ -321,6 +342,22 @@ def lib():
     L.spring_gzip_download.argtypes = [vp, u8p, vp]
     L.spring_gzip_write.argtypes = [vp, C.c_char_p, C.c_int32, C.POINTER(GzipInfo)]
     L.spring_gzip_get_info.argtypes = [vp, C.POINTER(GzipInfo)]
+    L.spring_bwt_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.spring_bwt_destroy.argtypes = [vp]
+    L.spring_bwt_destroy.restype = None
+    L.spring_bwt_set_block_bytes.argtypes = [vp, C.c_uint64]
+    L.spring_bwt_set_workspace_bytes.argtypes = [vp, C.c_uint64]
+    L.spring_bwt_workspace_need.argtypes = [C.c_uint64, C.c_uint64]
+    L.spring_bwt_workspace_need.restype = C.c_uint64
+    L.spring_bwt_from_host.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint64, C.POINTER(BwtInfo)]
+    L.spring_bwt_from_streams.argtypes = [vp, vp, C.c_uint32, C.POINTER(BwtInfo)]
+    L.spring_bwt_download.argtypes = [vp, u8p, vp, vp, vp, vp]
+    L.spring_bwt_segments.argtypes = [vp, vp, vp, vp]
+    L.spring_bwt_get_info.argtypes = [vp, C.POINTER(BwtInfo)]
+    L.spring_bwt_encode_inplace.argtypes = [vp, u8p, C.c_int32, vp, vp]
+    for name in BWT_EXPORTS:
+        if name not in ("spring_bwt_destroy", "spring_bwt_workspace_need"):
+            getattr(L, name).restype = C.c_int
     for name in GZIP_EXPORTS:
         if name != "spring_gzip_destroy":
             getattr(L, name).restype = C.c_int
