@@ -37,6 +37,8 @@ constexpr uint32_t ALT_MAX_READS = (1u << 27) - 1;
 // candidate of a chain that lost pass 0) writes ALT_KEY | chain id -- an earlier pass beats a later one, inside a pass the
 // lowest chain id wins (specification: orc_reorder_rounds_alt); chain ids stay below 2^28
 constexpr uint32_t ALT_KEY = 1u << 28;
+// DevParams::ord: bit 31 of a class-list entry = "this chain's proposal was lost" (local chain indices stay below 2^28 too)
+constexpr uint32_t ORD_LOST = 1u << 31;
 
 // Per-chain state (one greedy chain == one reference OpenMP thread, reorder.h:351-431).
 // The 64-byte header is wave-uniform: the chain kernels fetch it with ONE scalar load into 16 SGPRs (no VGPRs, no
@@ -71,7 +73,8 @@ static_assert(sizeof(ChainHot) == 64, "ChainHot must be one 64-byte line");
 struct __attribute__((aligned(64))) Chain {
   ChainHot h;
   uint64_t ref[16];      // consensus, 2 bits/base (reorder.h:371)
-  uint64_t revref[16];   // its reverse complement
+  uint64_t revref[16];   // its reverse complement (the one-chain kernels; k_round_mc rebuilds it from ref and keeps only its
+                         // known-absent masks here, in [8..15])
   uint64_t st_probes, st_keyok, st_cands, st_iter, st_lost, st_hits, n_unmatched, st_long /* searches finished by k_long */;
 #ifdef SR_PHASE_TIMING  // experiment builds (tools/xbuild.sh): shader clocks per phase of k_round, [32 + k] = visits
   uint64_t pt[64];
@@ -173,6 +176,8 @@ struct DevParams {
   // next round will ask of them -- 0 left search after a failed right search, 1 first search of a new seed, 2 search
   // after a proposed match, 3 seed pick -- into ord[block * MARK_BLOCK ...] (local chain indices, class 0 first) and
   // writes the four class sizes to ord_cnt[block].  No atomics, rewritten every round; done chains are in no list.
+  // An entry also carries the mark step's verdict on the chain's proposal: ORD_LOST is set when the chain proposed a match
+  // or a seed and did not secure the read -- the apply half of k_round_mc takes it from here instead of asking resv[].
   uint32_t *ord;
   uint4 *ord_cnt;
   // long searches (deep-bin pools, k_long): [0] = searches k_round handed over this round, [1] = k_long's ticket counter, [2 + i] = their local chain

@@ -2799,7 +2799,7 @@ __global__ void k_alt_resolve(DevParams P) {
 __global__ __launch_bounds__(256) void k_mg_mark(DevParams P) {
   const uint32_t cid = blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63;
-  bool needy = false, alive = false;
+  bool needy = false, alive = false, lost = false;  // lost: the chain proposed a match or a seed and did not secure it
   int cls = -1;  // class of the chain's next round (k_round_mc), local chains that are still running only
   if (cid < P.Ktot) {
     const unsigned long long pv = P.prop[cid];
@@ -2821,6 +2821,7 @@ __global__ __launch_bounds__(256) void k_mg_mark(DevParams P) {
         if (pk == PK_MATCH) atomicSub(&P.ublk[rid >> UBLK_SHIFT], 1u);
       }
       if (pv & PK_CURSOR_BIT) *P.cursor = (long long)(uint32_t)pv - 1;  // every seed proposed this round ends up taken
+      lost = !won;
       needy = pk == PK_SEED && !won;
       if (pk == PK_SEED && won && cls >= 0) cls = 1;
     } else if (pk == PK_NONE) {
@@ -2859,7 +2860,7 @@ __global__ __launch_bounds__(256) void k_mg_mark(DevParams P) {
       uint32_t base = 0;
       for (int k = 0; k < cls; k++) base += s_wc[0][k] + s_wc[1][k] + s_wc[2][k] + s_wc[3][k];
       for (int w = 0; w < wv; w++) base += s_wc[w][cls];
-      P.ord[(size_t)blockIdx.x * MARK_BLOCK + base + mypos] = cid - P.c0;
+      P.ord[(size_t)blockIdx.x * MARK_BLOCK + base + mypos] = (cid - P.c0) | (lost ? ORD_LOST : 0u);  // (the verdict: apply_mc)
     }
     if (threadIdx.x == 0)
       P.ord_cnt[blockIdx.x] = make_uint4(s_wc[0][0] + s_wc[1][0] + s_wc[2][0] + s_wc[3][0], s_wc[0][1] + s_wc[1][1] + s_wc[2][1] + s_wc[3][1],
@@ -2905,6 +2906,7 @@ __global__ __launch_bounds__(64) void k_ph_mark(DevParams P) {
     rs[j] = (pk == PK_MATCH || pk == PK_SEED) ? P.resv[(uint32_t)pv[j]] : 0xffffffffu;
   }
   int cls[CPL];
+  uint32_t lostm = 0;  // bit j: chain j of this lane proposed a match or a seed and did not secure it (ORD_LOST)
 #pragma unroll
   for (int j = 0; j < CPL; j++) {
     const uint32_t cid = cbase + 64 * j + lane;
@@ -2932,6 +2934,7 @@ __global__ __launch_bounds__(64) void k_ph_mark(DevParams P) {
           wonv = rid | (pk == PK_MATCH ? 0x80000000u : 0u);
         }
         if (pv[j] & PK_CURSOR_BIT) *P.cursor = (long long)(uint32_t)pv[j] - 1;  // every seed proposed this round ends up taken (by someone)
+        if (!won) lostm |= 1u << j;
         needy = pk == PK_SEED && !won;
         if (pk == PK_SEED && won && cls[j] >= 0) cls[j] = 1;
       } else if (pk == PK_NONE) {
@@ -2972,7 +2975,9 @@ __global__ __launch_bounds__(64) void k_ph_mark(DevParams P) {
 #pragma unroll
       for (int j = 0; j < CPL; j++) {
         const uint64_t m = __ballot(cls[j] == k);
-        if (cls[j] == k) P.ord[(size_t)segi * MARK_BLOCK + run + (uint32_t)__popcll(m & ((1ull << lane) - 1))] = cbase + 64 * j + lane - P.c0;
+        if (cls[j] == k)
+          P.ord[(size_t)segi * MARK_BLOCK + run + (uint32_t)__popcll(m & ((1ull << lane) - 1))] =
+              (cbase + 64 * j + lane - P.c0) | (((lostm >> j) & 1u) ? ORD_LOST : 0u);
         run += (uint32_t)__popcll(m);
       }
       tot[k] = run - base;
@@ -2989,7 +2994,7 @@ __global__ __launch_bounds__(256) void k_ph_mark_wide(DevParams P) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t cid = P.gg0 + t, gend = P.gg0 + P.gKg;  // (global chain ids, as in k_ph_mark)
   const int lane = threadIdx.x & 63;
-  bool needy = false, alive = false;
+  bool needy = false, alive = false, lost = false;  // lost: as in k_mg_mark
   int cls = -1;
   // The step sits on its group's critical path (round kernel -> mark -> round kernel) and is pure latency: independent loads
   // are issued together -- the proposal word and this thread's entry of the other group's winners first, then the reservation
@@ -3027,6 +3032,7 @@ __global__ __launch_bounds__(256) void k_ph_mark_wide(DevParams P) {
         wonv = rid | (pk == PK_MATCH ? 0x80000000u : 0u);
       }
       if (pv & PK_CURSOR_BIT) *P.cursor = (long long)(uint32_t)pv - 1;  // every seed proposed this round ends up taken (by someone)
+      lost = !won;
       needy = pk == PK_SEED && !won;
       if (pk == PK_SEED && won && cls >= 0) cls = 1;
     } else if (pk == PK_NONE) {
@@ -3072,7 +3078,7 @@ __global__ __launch_bounds__(256) void k_ph_mark_wide(DevParams P) {
       uint32_t base = 0;
       for (int k = 0; k < cls; k++) base += s_wc[0][k] + s_wc[1][k] + s_wc[2][k] + s_wc[3][k];
       for (int w = 0; w < wv; w++) base += s_wc[w][cls];
-      P.ord[(size_t)segi * MARK_BLOCK + base + mypos] = cid - P.c0;
+      P.ord[(size_t)segi * MARK_BLOCK + base + mypos] = (cid - P.c0) | (lost ? ORD_LOST : 0u);
     }
     if (threadIdx.x == 0)
       P.ord_cnt[segi] = make_uint4(s_wc[0][0] + s_wc[1][0] + s_wc[2][0] + s_wc[3][0], s_wc[0][1] + s_wc[1][1] + s_wc[2][1] + s_wc[3][1],
@@ -3097,7 +3103,7 @@ __global__ void k_delay(uint32_t us) {
   const uint64_t t0 = wall_clock64();  // 100 MHz
   while (wall_clock64() - t0 < (uint64_t)us * 100u) __builtin_amdgcn_s_sleep(64);
 }
-// first round: every local chain in class 2
+// first round: every local chain in class 2, no verdicts (PROP_FRESH: nothing proposed yet)
 // (over the global chains [gg0, gg0 + gKg) of the launch's group, gg0 a multiple of MARK_BLOCK; this rank's are [c0 + g0, c0 + g0 + Kg))
 __global__ void k_init_ord(DevParams P) {
   const uint32_t cid = P.gg0 + blockIdx.x * blockDim.x + threadIdx.x;  // global chain id; block = the mark step's block

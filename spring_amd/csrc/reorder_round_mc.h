@@ -191,7 +191,15 @@ __device__ __forceinline__ int update_mc(const DevParams &P, uint32_t li, GLds<N
   return Rn;
 }
 
-// commit of a speculative update: S.nref -> ref (LDS + global), revref = its reverse complement (LDS + global)
+// Limb gl of revref = the reverse complement of ref[0, R), from the LDS copy of ref (sref = S.refs[0] + PAD, zero limbs in
+// front): bases [32 gl, 32 gl + 32) of it are the ref bases R - 1 - 32 gl downwards, complemented (sf::rc_limb, which the
+// host-side test checks base by base).  Zero from limb ceil(R / 32) on.
+__device__ __forceinline__ uint64_t revref_limb(const uint64_t *sref, int R, int gl) {
+  return 32 * gl < R ? sf::rc_limb(lds_window(sref, sf::rc_limb_bitpos(R, gl)), R - 32 * gl) : 0ull;
+}
+
+// commit of a speculative update: S.nref -> ref (LDS + global), revref = its reverse complement (LDS only: the next round
+// rebuilds it from ref and ref_len, round_mc_body)
 template <int NQ, bool KA>
 __device__ __forceinline__ void commit_consensus(const DevParams &P, GLds<NQ, KA> &S, Chain *c, int R, int gl) {
   constexpr int LDS_PAD = GLds<NQ, KA>::PAD;
@@ -201,17 +209,7 @@ __device__ __forceinline__ void commit_consensus(const DevParams &P, GLds<NQ, KA
   if (gl < GLds<NQ, KA>::WMAX) S.refs[0][LDS_PAD + gl] = limb;
   if (in) c->ref[gl] = limb;
   wave_sync();
-  uint64_t rl = 0;
-  if (in && 32 * gl < R) {
-    // bases [32 gl, 32 gl + 32) of the reverse complement = ref bases R-1-32gl downwards, complemented
-    const uint64_t w = lds_window(S.refs[0] + LDS_PAD, 2 * (R - 32 - 32 * gl));
-    uint64_t x = __builtin_bitreverse64(w);
-    x = ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
-    const int nv = R - 32 * gl;
-    rl = ~x & (nv >= 32 ? ~0ull : ((1ull << (2 * nv)) - 1));
-  }
-  if (gl < GLds<NQ, KA>::WMAX) S.refs[1][LDS_PAD + gl] = rl;
-  if (in) c->revref[gl] = rl;
+  if (gl < GLds<NQ, KA>::WMAX) S.refs[1][LDS_PAD + gl] = revref_limb(S.refs[0] + LDS_PAD, R, gl);
   wave_sync();
 }
 
@@ -267,14 +265,7 @@ __device__ __forceinline__ void commit_consensus_ka(const DevParams &P, GLds<NQ,
   if (gl < WM) { S.refs[0][LDS_PAD + gl] = limb; S.ka[0][LDS_PAD + gl] = kf; }
   if (in) c->ref[gl] = limb;
   wave_sync();
-  uint64_t rl = 0;
-  if (in && 32 * gl < R) {
-    const uint64_t w = lds_window(S.refs[0] + LDS_PAD, 2 * (R - 32 - 32 * gl));
-    uint64_t x = __builtin_bitreverse64(w);
-    x = ((x >> 1) & EVEN) | ((x & EVEN) << 1);
-    const int nv = R - 32 * gl;
-    rl = ~x & (nv >= 32 ? ~0ull : ((1ull << (2 * nv)) - 1));
-  }
+  const uint64_t rl = gl < WM ? revref_limb(S.refs[0] + LDS_PAD, R, gl) : 0ull;
   if (mode == 0) {
     if (gl < WM) {
       uint64_t x = rl ^ lds_window(S.refs[1] + LDS_PAD, 64 * gl + 2 * dlt);
@@ -288,8 +279,7 @@ __device__ __forceinline__ void commit_consensus_ka(const DevParams &P, GLds<NQ,
     kr &= ~ka_stale(dr, gshfl_down1_u64(dr));
   }
   wave_sync();
-  if (gl < WM) { S.refs[1][LDS_PAD + gl] = rl; S.ka[1][LDS_PAD + gl] = kr; }
-  if (in) c->revref[gl] = rl;
+  if (gl < WM) { S.refs[1][LDS_PAD + gl] = rl; S.ka[1][LDS_PAD + gl] = kr; }  // (revref stays in LDS: commit_consensus)
   wave_sync();
 }
 
@@ -328,8 +318,12 @@ __device__ __forceinline__ void emit_single_mc(const DevParams &P, ChainHot &h, 
 }
 
 // phase B of one chain (apply_step with the shared state deferred to k_mg_mark).  false: the chain is done.
+// lost: the mark step's verdict on the chain's proposal (ORD_LOST of its class-list entry).  It is what resv[prop_rid] !=
+// cid says in apply_step: the mark step computed `won` from that very word, after every reservation of the round, and where
+// it overrules a chain that still holds the word (the other group took the read) it writes RESV_LOST there; nothing claims
+// the word for this chain afterwards.  So nothing is asked of resv[] here, and a lost proposal costs no update.
 template <int NQ, bool KA>
-__device__ __forceinline__ bool apply_mc(const DevParams &P, Chain *c, uint32_t cid, uint32_t li, ChainHot &h, GLds<NQ, KA> &S, int gl) {
+__device__ __forceinline__ bool apply_mc(const DevParams &P, Chain *c, uint32_t li, ChainHot &h, GLds<NQ, KA> &S, int gl, bool lost) {
   const int kind = h.prop_kind;
   if (kind == PROP_FRESH) return true;  // first round: nothing proposed yet
   if (h.finishing) {  // seed-needing chain found the pool empty
@@ -338,7 +332,12 @@ __device__ __forceinline__ bool apply_mc(const DevParams &P, Chain *c, uint32_t 
     store_hot(c, h, gl);
     return false;
   }
-  const uint32_t owner = kind != PROP_NONE ? P.resv[h.prop_rid] : cid;  // in flight while the update is computed
+  if (lost) {  // (a match or a seed) lost the read: retry, nothing committed
+    if (h.mode == MODE_SEARCH) h.retrying = 1;
+    store_hot(c, h, gl, 3, 4);
+    if (gl == 0) atomicAdd((unsigned long long *)&c->st_lost, 1ull);
+    return true;
+  }
   const bool fail_path = kind == PROP_NONE && h.mode == MODE_SEARCH;
   bool do_upd = false, ureset = false, urev = false;
   uint32_t urid = 0;
@@ -359,12 +358,6 @@ __device__ __forceinline__ bool apply_mc(const DevParams &P, Chain *c, uint32_t 
       wave_sync();
       R_new = update_mc<NQ, KA>(P, li, S, urid, n, ureset, urev, ushift, R_old, (int)h.cnt_buf, h.cnt_wide != 0, true, o2, gl);
     }
-  }
-  if (owner != cid) {  // lost the read: retry, nothing committed
-    if (h.mode == MODE_SEARCH) h.retrying = 1;
-    store_hot(c, h, gl, 3, 4);
-    if (gl == 0) atomicAdd((unsigned long long *)&c->st_lost, 1ull);
-    return true;
   }
   if (do_upd) {
     if constexpr (KA) {
@@ -1214,6 +1207,7 @@ __device__ __forceinline__ void round_mc_body(const DevParams &P) {
   // of the list (each empty block costs ~1.3 ns of dispatch: 547 ms), and resident wavefronts looping over the list
   // (the loop costs the body 30 VGPRs, an occupancy step: 487-710 ms).
   uint32_t li;
+  bool lost, seeker;
   {
     const uint32_t seg = (P.c0 + P.g0) / MARK_BLOCK + blockIdx.x / MC_WAVES_PER_BLOCK, b = blockIdx.x % MC_WAVES_PER_BLOCK;
     const uint4 n = P.ord_cnt[seg];
@@ -1225,7 +1219,10 @@ __device__ __forceinline__ void round_mc_body(const DevParams &P) {
     const uint32_t lbase = cls == 0 ? 0u : cls == 1 ? n.x : cls == 2 ? n.x + n.y : n.x + n.y + n.z;
     const uint32_t j = (b - wbase) * mc::CPW + (uint32_t)g;
     if (j >= cnt) return;  // (whole groups leave; the others never wait for them: no block barriers below)
-    li = P.ord[(size_t)seg * MARK_BLOCK + lbase + j];
+    const uint32_t e = P.ord[(size_t)seg * MARK_BLOCK + lbase + j];
+    li = e & ~ORD_LOST;
+    lost = (e & ORD_LOST) != 0;  // the mark step's verdict on the chain's proposal (apply_mc)
+    seeker = cls == 3;           // (uniform over the wavefront)
   }
   const uint32_t cid = P.c0 + li;
   Chain *c = &P.chains[li];
@@ -1234,20 +1231,27 @@ __device__ __forceinline__ void round_mc_body(const DevParams &P) {
   {
     const uint4 *hq = reinterpret_cast<const uint4 *>(&c->h);
     const uint4 q0 = hq[0], q1 = hq[1], q2 = hq[2], q3 = hq[3];
-    if constexpr (KA) {  // the chain's known-absent masks: four limbs of either strand (commit_consensus_ka); the rest is zero
-      static_assert(GL::LIMBS <= mc::G, "one limb per lane");
-      const uint64_t kav = gl < 8 ? c->revref[8 + gl] : 0ull;
-      if (gl < GL::LIMBS) { S.ka[0][gl] = 0ull; S.ka[1][gl] = 0ull; }
-      wave_sync();
-      if (gl < 8) S.ka[gl >> 2][GL::PAD + (gl < 4 ? P.ka_lo : 0) + (gl & 3)] = kav;
+    // A chain of class 3 picks a seed this round and looks at no consensus: its header is all it loads.  The class holds the
+    // chains whose left search failed or was not run (PK_NONE | PK_WILLNEED: apply_mc updates nothing when left_search is set, and sends the
+    // chain for a seed), those whose seed was lost (the verdict is in the list entry: apply_mc returns before any update --
+    // a seed that was won is in class 1) and those that found the pool empty (finishing: apply_mc emits and leaves); what
+    // is left of them runs find_seed_mc and returns from search_mc in MODE_NEED_SEED.  None of that reads or writes S.refs,
+    // S.ka, S.rd or S.nref, and the masks are only stored for a chain in MODE_SEARCH (below).
+    if (!seeker) {
+      if constexpr (KA) {  // the chain's known-absent masks: four limbs of either strand (commit_consensus_ka); the rest is zero
+        static_assert(GL::LIMBS <= mc::G, "one limb per lane");
+        const uint64_t kav = gl < 8 ? c->revref[8 + gl] : 0ull;
+        if (gl < GL::LIMBS) { S.ka[0][gl] = 0ull; S.ka[1][gl] = 0ull; }
+        wave_sync();
+        if (gl < 8) S.ka[gl >> 2][GL::PAD + (gl < 4 ? P.ka_lo : 0) + (gl & 3)] = kav;
+      }
+      for (int i = gl; i < GL::LIMBS; i += mc::G) {  // ref, and the zero limbs either side of ref and revref
+        const int k = i - GL::PAD;
+        S.refs[0][i] = k >= 0 && k < P.W ? c->ref[k] : 0ull;
+        if (k < 0 || k >= GL::WMAX) S.refs[1][i] = 0ull;
+      }
+      if (gl < 2) S.rd[gl ? GL::WMAX + 1 : 0] = 0ull;
     }
-    for (int i = gl; i < GL::LIMBS; i += mc::G) {
-      const int k = i - GL::PAD;
-      const bool in = k >= 0 && k < P.W;
-      S.refs[0][i] = in ? c->ref[k] : 0ull;
-      S.refs[1][i] = in ? c->revref[k] : 0ull;
-    }
-    if (gl < 2) S.rd[gl ? GL::WMAX + 1 : 0] = 0ull;
     h.ref_pos = (long long)(((unsigned long long)q0.y << 32) | q0.x);
     h.ref_len = (int32_t)q0.z; h.e_slot = q0.w;
     h.prev = q1.x; h.first_rid = q1.y; h.n_emit = q1.z; h.n_single = q1.w;
@@ -1261,14 +1265,18 @@ __device__ __forceinline__ void round_mc_body(const DevParams &P) {
     if (gl == 0) P.prop[cid] = (unsigned long long)PK_DONE << 32;
     return;
   }
+  if (!seeker) {  // revref = the reverse complement of ref[0, ref_len): rebuilt, not kept in the chain record (commit_consensus)
+    if (gl < GL::WMAX) S.refs[1][GL::PAD + gl] = mc::revref_limb(S.refs[0] + GL::PAD, h.ref_len, gl);
+    wave_sync();
+  }
   PTW(16);
-  if (!mc::apply_mc<NQ, KA>(P, c, cid, li, h, S, gl)) {
+  if (!mc::apply_mc<NQ, KA>(P, c, li, h, S, gl, lost)) {
     if (gl == 0) P.prop[cid] = (unsigned long long)PK_DONE << 32;
     return;
   }
   PT(17);
   mc::search_mc<NQ, MG, KA>(P, c, cid, h, S, (lds_u32_t *)s_stage, lane, gl);
-  if constexpr (KA) if (h.mode == MODE_SEARCH) {  // what the chain knows now, for its next round
+  if constexpr (KA) if (!seeker && h.mode == MODE_SEARCH) {  // what the chain knows now, for its next round
     wave_sync();
     if (gl < 8) c->revref[8 + gl] = S.ka[gl >> 2][GL::PAD + (gl < 4 ? P.ka_lo : 0) + (gl & 3)];
   }

@@ -56,6 +56,14 @@ SF_FN uint64_t rc_window(uint64_t w, int wl) {
   x = ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);  // bases reversed, bits of a base in order
   return ~x >> (64 - 2 * wl);
 }
+// Limb j (bases [32 j, 32 j + 32)) of the reverse complement of the first R bases of a consensus, 32 j < R (the four-chain
+// round kernel rebuilds a chain's reverse consensus with it instead of keeping a copy): it is made of the 64 consensus bits
+// from bit rc_limb_bitpos(R, j) on -- bits in front of base 0 read as zero -- and holds nv = R - 32 j bases (the top limb:
+// fewer than 32, the rest zero).
+SF_FN int rc_limb_bitpos(int R, int j) { return 2 * (R - 32 - 32 * j); }
+SF_FN uint64_t rc_limb(uint64_t w, int nv) {
+  return rc_window(w, 32) & (nv >= 32 ? ~0ull : ((1ull << (2 * nv)) - 1));
+}
 SF_FN uint64_t canon(uint64_t w, int wl, bool &swapped) {
   const uint64_t r = rc_window(w, wl);
   swapped = r < w;
