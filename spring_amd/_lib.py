@@ -65,6 +65,14 @@ BWT_EXPORTS = [
 ]
 BWT_MAX_INDEXES = 256  # SPRING_BWT_MAX_INDEXES
 
+# include/spring_unbwt.h: a list of its own as well
+UNBWT_EXPORTS = [
+    "spring_unbwt_create", "spring_unbwt_destroy", "spring_unbwt_set_workspace_bytes", "spring_unbwt_workspace_need",
+    "spring_unbwt_set_head_spacing", "spring_unbwt_from_host", "spring_unbwt_from_bwt", "spring_unbwt_download",
+    "spring_unbwt_get_info", "spring_unbwt_decode_inplace",
+]
+UNBWT_PASSES = 6  # SPRING_UNBWT_PASSES
+
 
 class Opts(C.Structure):
     _fields_ = [("device", C.c_int32), ("num_chains", C.c_uint32), ("num_thr", C.c_int32),
@@ -162,6 +170,19 @@ class BwtInfo(C.Structure):
     _fields_ = ([(k, C.c_uint64) for k in ("num_segments", "bytes", "max_segment", "sub_batches", "rounds",
                                            "rounds_total", "workspace_bytes")]
                 + [("ms_device", C.c_double), ("ms_pass", C.c_double * 5)])
+
+    def asdict(self):
+        d = {}
+        for k, _ in self._fields_:
+            v = getattr(self, k)
+            d[k] = list(v) if hasattr(v, "__len__") else v
+        return d
+
+
+class UnbwtInfo(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("num_segments", "bytes", "max_segment", "sub_batches", "heads", "head_spacing",
+                                           "max_walk", "rank_rounds", "workspace_bytes")]
+                + [("ms_device", C.c_double), ("ms_pass", C.c_double * UNBWT_PASSES)])
 
     def asdict(self):
         d = {}
@@ -355,6 +376,21 @@ def lib():
     L.spring_bwt_segments.argtypes = [vp, vp, vp, vp]
     L.spring_bwt_get_info.argtypes = [vp, C.POINTER(BwtInfo)]
     L.spring_bwt_encode_inplace.argtypes = [vp, u8p, C.c_int32, vp, vp]
+    L.spring_unbwt_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.spring_unbwt_destroy.argtypes = [vp]
+    L.spring_unbwt_destroy.restype = None
+    L.spring_unbwt_set_workspace_bytes.argtypes = [vp, C.c_uint64]
+    L.spring_unbwt_workspace_need.argtypes = [C.c_uint64, C.c_uint64]
+    L.spring_unbwt_workspace_need.restype = C.c_uint64
+    L.spring_unbwt_set_head_spacing.argtypes = [vp, C.c_uint32]
+    L.spring_unbwt_from_host.argtypes = [vp, u8p, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(UnbwtInfo)]
+    L.spring_unbwt_from_bwt.argtypes = [vp, vp, C.POINTER(UnbwtInfo)]
+    L.spring_unbwt_download.argtypes = [vp, u8p, vp]
+    L.spring_unbwt_get_info.argtypes = [vp, C.POINTER(UnbwtInfo)]
+    L.spring_unbwt_decode_inplace.argtypes = [vp, u8p, C.c_int32, C.c_int32, C.c_uint8, vp]
+    for name in UNBWT_EXPORTS:
+        if name not in ("spring_unbwt_destroy", "spring_unbwt_workspace_need"):
+            getattr(L, name).restype = C.c_int
     for name in BWT_EXPORTS:
         if name not in ("spring_bwt_destroy", "spring_bwt_workspace_need"):
             getattr(L, name).restype = C.c_int

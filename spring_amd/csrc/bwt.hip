@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <rocprim/rocprim.hpp>
 
+#include "bwt_internal.h"
 #include "bwt_plan.h"
 #include "reorder_device.h"
 #include "reorder_internal.h"
@@ -589,3 +590,13 @@ int spring_bwt_encode_inplace(spring_bwt_ctx *ctx, uint8_t *T, int32_t n, uint8_
 }
 
 }  // extern "C"
+
+namespace sr {
+int bwt_view(spring_bwt_ctx *ctx, BwtView *v) {
+  if (!ctx || !v) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  if (!ctx->have) return fail(SPRING_REORDER_E_STATE, "nothing transformed yet");
+  *v = BwtView{ctx->dev, ctx->info.num_segments, ctx->info.bytes, ctx->out.as<uint8_t>(), ctx->primary.as<int32_t>(),
+               ctx->off.data()};
+  return 0;
+}
+}  // namespace sr
