@@ -56,6 +56,7 @@ typedef struct {
   double ms_device;         /* HIP events around the device passes, input copies excluded          */
   double ms_file;           /* spring_gzip_write: wall time of the last call                       */
   double ms_pass[6];        /* chunk table, match + parse, codes, emit, CRC-32, compaction         */
+  uint64_t num_batches;     /* batches the chunks were matched, coded and emitted in (0: stored)   */
 } spring_gzip_info;
 
 int spring_gzip_create(int device, spring_gzip_ctx **out);
@@ -64,6 +65,10 @@ void spring_gzip_destroy(spring_gzip_ctx *ctx);
 /* chunk_bytes for the calls that follow: a multiple of 4096 in 4096 .. 65536 (for measurements; the default is the
  * measured choice of DESIGN.md section 14).  The match window is min(32768, 65536 - chunk_bytes). */
 int spring_gzip_set_chunk_bytes(spring_gzip_ctx *ctx, uint32_t chunk_bytes);
+/* Token scratch of one batch of chunks for the calls that follow; 0 selects the default of 1 GiB.  Chunks are matched,
+ * coded and emitted max(1, bytes / (chunk_bytes * 4)) at a time (info.num_batches batches).  For tests and
+ * measurements: the output does not depend on it. */
+int spring_gzip_set_token_bytes(spring_gzip_ctx *ctx, uint64_t bytes);
 
 int spring_gzip_from_fastq_out(spring_gzip_ctx *ctx, spring_fastq_out_ctx *text, uint64_t member_records, int32_t mode,
                                spring_gzip_info *info);

@@ -53,8 +53,9 @@ FASTQ_OUT_EXPORTS = [
 
 # include/spring_gzip.h: a list of its own as well
 GZIP_EXPORTS = [
-    "spring_gzip_create", "spring_gzip_destroy", "spring_gzip_set_chunk_bytes", "spring_gzip_from_fastq_out",
-    "spring_gzip_from_host", "spring_gzip_download", "spring_gzip_write", "spring_gzip_get_info",
+    "spring_gzip_create", "spring_gzip_destroy", "spring_gzip_set_chunk_bytes", "spring_gzip_set_token_bytes",
+    "spring_gzip_from_fastq_out", "spring_gzip_from_host", "spring_gzip_download", "spring_gzip_write",
+    "spring_gzip_get_info",
 ]
 
 # include/spring_bwt.h: a list of its own as well
@@ -156,7 +157,8 @@ class FastqOutInfo(C.Structure):
 class GzipInfo(C.Structure):
     _fields_ = ([(k, C.c_uint64) for k in ("num_members", "bytes_in", "bytes_out", "chunk_bytes", "num_chunks",
                                            "chunks_stored")]
-                + [("ms_device", C.c_double), ("ms_file", C.c_double), ("ms_pass", C.c_double * 6)])
+                + [("ms_device", C.c_double), ("ms_file", C.c_double), ("ms_pass", C.c_double * 6),
+                   ("num_batches", C.c_uint64)])
 
     def asdict(self):
         d = {}
@@ -358,6 +360,7 @@ def lib():
     L.spring_gzip_destroy.argtypes = [vp]
     L.spring_gzip_destroy.restype = None
     L.spring_gzip_set_chunk_bytes.argtypes = [vp, C.c_uint32]
+    L.spring_gzip_set_token_bytes.argtypes = [vp, C.c_uint64]
     L.spring_gzip_from_fastq_out.argtypes = [vp, vp, C.c_uint64, C.c_int32, C.POINTER(GzipInfo)]
     L.spring_gzip_from_host.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint64, C.c_int32, C.POINTER(GzipInfo)]
     L.spring_gzip_download.argtypes = [vp, u8p, vp]

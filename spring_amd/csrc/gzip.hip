@@ -42,7 +42,7 @@ constexpr int HASH_BITS = 14;                  // 16384 slots of 16 bits: 32 KiB
 constexpr int INTRA = 16;                      // candidates looked for among the lanes below, this far
 constexpr uint32_t STORED_MAX = 65535;
 constexpr uint32_t F_FIRST = 1, F_LAST = 2, F_STORED = 4;
-constexpr uint32_t BATCH_TOKEN_BYTES = 1u << 30;   // token scratch of one batch of chunks
+constexpr uint64_t BATCH_TOKEN_BYTES = 1ull << 30;   // token scratch of one batch of chunks
 constexpr int EMIT_T = 256;
 constexpr int STAGE_WORDS = EMIT_T * 48 / 32 + 4;
 
@@ -517,6 +517,7 @@ struct spring_gzip_ctx {
   int dev = 0;
   hipStream_t st = nullptr;
   uint32_t chunk_bytes = DEFAULT_CHUNK;
+  uint64_t token_bytes = BATCH_TOKEN_BYTES;
   bool have = false;
   spring_gzip_info info;
   DBuf out, out_off, cfirst;   // the members; per chunk and per member where they start
@@ -598,7 +599,7 @@ int compress(spring_gzip_ctx *ctx, const uint8_t *t, uint64_t nbytes, const uint
     HIPCHK(sr::excl_scan_u32_to_u64(st, tmp.p, tbs, seg.as<uint32_t>(), C.slot_off, NC + 1));
     DALLOC(slots, nbytes + NC * 48 + 32);   // the sum of the slot sizes is at most this
     C.slots = slots.as<uint8_t>();
-    const uint64_t batch = std::min<uint64_t>(NC, std::max<uint64_t>(1, BATCH_TOKEN_BYTES / ((uint64_t)chunk * 4)));
+    const uint64_t batch = std::min<uint64_t>(NC, std::max<uint64_t>(1, ctx->token_bytes / ((uint64_t)chunk * 4)));
     DALLOC(tokens, batch * chunk * 4);
     DALLOC(codes, batch * sizeof(gz::ChunkCode));
     Events bev;
@@ -618,6 +619,7 @@ int compress(spring_gzip_ctx *ctx, const uint8_t *t, uint64_t nbytes, const uint
       HIPCHK(hipEventElapsedTime(&b, bev.e[1], bev.e[2]));
       HIPCHK(hipEventElapsedTime(&c, bev.e[2], bev.e[3]));
       ms_match += a; ms_codes += b; ms_emit += c;
+      I.num_batches++;
     }
     HIPCHK(hipGetLastError());
   }
@@ -722,6 +724,12 @@ int spring_gzip_set_chunk_bytes(spring_gzip_ctx *ctx, uint32_t chunk_bytes) {
   if (chunk_bytes < 4096 || chunk_bytes > 65536 || chunk_bytes % 4096)
     return fail(SPRING_REORDER_E_ARG, "chunk_bytes must be a multiple of 4096 in 4096 .. 65536 (got %u)", chunk_bytes);
   ctx->chunk_bytes = chunk_bytes;
+  return 0;
+}
+
+int spring_gzip_set_token_bytes(spring_gzip_ctx *ctx, uint64_t bytes) {
+  if (!ctx) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  ctx->token_bytes = bytes ? bytes : BATCH_TOKEN_BYTES;
   return 0;
 }
 

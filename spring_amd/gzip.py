@@ -47,6 +47,11 @@ class GzipStage:
         """The cut inside a member for the calls that follow (for measurements; the default is the measured choice)."""
         _chk(self._L.spring_gzip_set_chunk_bytes(self._h, chunk_bytes))
 
+    def set_token_bytes(self, nbytes):
+        """Token scratch of one batch of chunks for the calls that follow (0: the default of 1 GiB).  For tests and
+        measurements: the output does not depend on it."""
+        _chk(self._L.spring_gzip_set_token_bytes(self._h, nbytes))
+
     def compress(self, src, member_records=0, member_off=None, mode=DEFLATE):
         """src: a FastqOutStage holding a text; members are cut every member_records records (0: one member).  Or
         bytes / a uint8 array; member_off: num_members + 1 offsets from 0 to len(src), strictly increasing (None: one

@@ -105,6 +105,36 @@ def contents(kind, n, seed=0):
     raise ValueError(kind)
 
 
+POOL_LENGTHS = {"acgt": (1, 7, 31, 64, 90, 150, 210, 256, 299, 300), "bytes": (2, 8, 15, 65, 100, 180, 255, 300),
+                "const": (1, 2, 3, 63, 150, 257, 300), "cac": (3, 9, 100, 300), "tail00": (3, 17, 128, 300),
+                "tailff": (3, 16, 64, 129, 300)}
+
+
+def segment_pool():
+    """38 distinct texts of 1 .. 300 bytes of every kind, and the empty one."""
+    pool = [b""] + [contents(kind, n, seed=5) for kind, lens in POOL_LENGTHS.items() for n in lens]
+    assert len(set(pool)) == len(pool) == 39 and max(len(t) for t in pool) == 300
+    return pool
+
+
+def pool_batch(S, seed=17):
+    """S segments drawn from segment_pool() (a model result per distinct text serves the whole batch): one segment in
+    nine is empty, one in eight repeats its neighbour, three empties stand in a row, and segments 40 and 8000 (where
+    the batch has them) are the 300 random bytes of ACGT and the 255 random bytes."""
+    pool = segment_pool()
+    rng = np.random.default_rng(seed * 1000003 + S)
+    idx = rng.integers(1, len(pool), S)
+    idx[rng.random(S) < 1 / 9] = 0
+    rep = np.flatnonzero(rng.random(S) < 1 / 8)
+    rep = rep[rep > 0]
+    idx[rep] = idx[rep - 1]
+    idx[5:8] = 0
+    for s, text in ((40, contents("acgt", 300, seed=5)), (8000, contents("bytes", 255, seed=5))):
+        if s < S:
+            idx[s] = pool.index(text)
+    return [pool[i] for i in idx]
+
+
 def dna_with_repeats(n, seed=3):
     """DNA-like text with planted repeats of 300 and 5000 bytes."""
     rng = np.random.default_rng(seed)

@@ -132,6 +132,59 @@ def test_sub_batches_give_the_same_result():
         _same(st.download(), segs, "after a refusal")
 
 
+# ------------------------------------------------------------------ the classes of the first key
+# The first sort key holds as many text bytes as the segment number leaves room for (bwt_plan.h::key_layout): 7 up to
+# 32 segments in a sub-batch, 6 up to 8192, 5 up to 2^21, 4 above; the doubling starts at that width.
+
+def key_bytes(sub_segments):
+    """bwt_plan.h::key_layout restated: text bytes in the first key of a sub-batch of this many segments."""
+    seg_bits = (max(sub_segments, 1) - 1).bit_length()
+    return min(7, (64 - 3 - seg_bits) // 8)
+
+
+def plan(segs, budget):
+    """bwt_plan.h::plan_sub_batches restated (72 bytes a position, 16 a segment) -> segments of every sub-batch."""
+    counts, m, k = [], 0, 0
+    for seg in segs:
+        if k and (m + len(seg)) * 72 + (k + 1) * 16 > budget:
+            counts.append(k)
+            m = k = 0
+        m, k = m + len(seg), k + 1
+    return counts + ([k] if k else [])
+
+
+CLASSES = ((32, 7), (33, 6), (8192, 6), (8193, 5))
+
+
+@functools.lru_cache(maxsize=None)
+def _pool_run(S):
+    segs = bm.pool_batch(S)
+    return (segs,) + _run(segs)
+
+
+@pytest.mark.parametrize("S,width", CLASSES)
+def test_segment_count_classes(S, width):
+    assert key_bytes(S) == width and [key_bytes(x) for x in (1, 1 << 21, (1 << 21) + 1)] == [7, 5, 4]
+    segs, res, info = _pool_run(S)
+    assert len(segs) == S and len(set(segs)) > 10 and b"" in segs and max(len(s) for s in segs) == 300
+    assert any(a == b != b"" for a, b in zip(segs, segs[1:]))   # equal neighbours
+    assert info["sub_batches"] == 1   # all S segments share one first key
+    _same(res, segs, "%d segments" % S)
+
+
+def test_the_5_byte_class_cut_into_7_byte_sub_batches():
+    from spring_amd.bwt import workspace_need
+    segs, one, info1 = _pool_run(8193)
+    budget = workspace_need(1200, 32)
+    counts = plan(segs, budget)
+    assert sum(counts) == 8193 and 2 <= max(counts) <= 32 and key_bytes(max(counts)) == 7 and key_bytes(8193) == 5
+    many, info = _run(segs, workspace=budget)
+    assert info1["sub_batches"] == 1 and info["sub_batches"] == len(counts) > 256
+    assert many["bwt"] == one["bwt"]
+    for k in ("seg_off", "primary", "num_indexes", "indexes"):
+        assert np.array_equal(many[k], one[k]), k
+
+
 def test_two_runs_give_identical_bytes():
     segs = _lengths_batch()
     a, _ = _run(segs)
@@ -237,6 +290,29 @@ def test_from_a_streams_context(name, pe, preserve_order, B):
         after = [ss.download(s) for s in range(9)]
         for (a, ao), (b, bo) in zip(before, after):   # the streams context is left as it was
             assert a == b and np.array_equal(ao, bo)
+
+
+def test_from_a_streams_context_in_more_than_8192_segments():
+    """One read a block and slices cut every 16 bytes: the 5-byte class of the first key from a streams context."""
+    from spring_amd.bwt import BwtStage
+    from spring_amd.streams import StreamsStage
+    with StreamsStage() as ss, BwtStage() as st, BwtStage() as host:
+        _streams_run(ss, "var2k", False, False, 1)
+        want = _slices(ss, 16)
+        assert len(want) > 8192 and key_bytes(len(want)) == 5
+        assert max(c for _, _, c, _ in want) >= 1 and len({s for s, _, _, _ in want}) >= 7   # slices are cut
+        st.set_block_bytes(16)
+        info = st.transform(ss)
+        assert info["num_segments"] == len(want) and info["max_segment"] == 16 and info["sub_batches"] == 1
+        stream, block, cut = st.segments()
+        assert [(int(a), int(b), int(c)) for a, b, c in zip(stream, block, cut)] == [w[:3] for w in want]
+        res = st.download()
+        segs = [w[3] for w in want]
+        _same(res, segs, "var2k, 16 bytes")
+        hres = (host.transform(*_batch(segs)), host.download())[1]
+        assert host.info["sub_batches"] == 1 and res["bwt"] == hres["bwt"]
+        for k in ("seg_off", "primary", "num_indexes", "indexes"):
+            assert np.array_equal(res[k], hres[k]), k
 
 
 def _bsc_block(seg, out, primary, idx, adler):

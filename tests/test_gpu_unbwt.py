@@ -257,6 +257,87 @@ def test_short_paths_are_refused():
         assert st.download()["text"] == text
 
 
+# ------------------------------------------------------------------ segment counts and head spacings
+# The stable sort runs over 40 + bits_for(segments) bits and the heads are laid out by the spacing K: the batches of
+# tests/test_gpu_bwt.py (32, 33, 8192 and 8193 segments) and every K the library takes.
+
+CLASSES = (32, 33, 8192, 8193)
+SPACINGS = (16, 32, 64, 128, 256, 512, 1024)
+
+
+@pytest.mark.parametrize("S", CLASSES)
+def test_segment_count_classes(S):
+    texts = bm.pool_batch(S)
+    assert len(texts) == S
+    _, info = _texts(texts, "%d segments" % S)
+    assert info["sub_batches"] == 1 and info["max_walk"] <= 300
+    assert info["heads"] == -(-(sum(len(t) for t in texts) + S) // 64) + 2 * S
+
+
+def test_from_a_block_sort_context_of_8193_segments():
+    from spring_amd.bwt import BwtStage
+    from spring_amd.unbwt import UnbwtStage
+    texts = bm.pool_batch(8193)
+    data, off = _batch(texts)
+    with BwtStage() as fw, UnbwtStage() as st:
+        assert fw.transform(data, off)["sub_batches"] == 1
+        info = st.invert(fw)
+        assert info["num_segments"] == 8193 and info["bytes"] == len(data) and info["sub_batches"] == 1
+        res = st.download()
+        assert res["text"] == data and np.array_equal(res["seg_off"], off)
+
+
+SPACING_INPUTS = {"lengths": _lengths_batch, "periodic": lambda: [PERIODIC[k] for k in sorted(PERIODIC)],
+                  "8193 segments": lambda: bm.pool_batch(8193), "70000 bytes": lambda: [bm.contents("acgt", 70000, seed=4)]}
+
+
+@pytest.mark.parametrize("what", sorted(SPACING_INPUTS))
+def test_every_head_spacing(what):
+    texts = SPACING_INPUTS[what]()
+    S, nbytes, longest = len(texts), sum(len(t) for t in texts), max(len(t) for t in texts)
+    first = None
+    for K in SPACINGS:
+        res, info = _texts(texts, (what, K), head_spacing=K)   # the model's text, and the texts themselves
+        assert info["head_spacing"] == K, (what, K)
+        assert 1 <= info["max_walk"] <= longest, (what, K, info["max_walk"])   # the bound of the walk is never reached
+        assert info["sub_batches"] == 1 and info["heads"] == -(-(nbytes + S) // K) + 2 * S, (what, K, info["heads"])
+        first = first or res
+        assert res["text"] == first["text"] and np.array_equal(res["seg_off"], first["seg_off"]), (what, K)
+
+
+def _short_primary(L, primary):
+    """A primary index whose path from row 0 is short (as test_short_paths_are_refused picks them)."""
+    for p in range(1, len(L) + 1):
+        if p != primary and um.path_length(L, p) < len(L):
+            return p
+    raise AssertionError("every primary index of this transform has a complete path")
+
+
+def test_short_paths_among_8193_segments_are_refused():
+    from spring_amd.reorder import ReorderError
+    from spring_amd.unbwt import UnbwtStage
+    pairs = [_fwd(t)[:2] for t in bm.pool_batch(8193)]
+    good = list(pairs)
+    for s in (8000, 40):
+        assert len(pairs[s][0]) >= 255
+        pairs[s] = (pairs[s][0], _short_primary(*pairs[s]))
+    data, off = _batch([p[0] for p in pairs])
+    with UnbwtStage() as st:
+        for K in (16, 64, 1024):
+            st.set_head_spacing(K)
+            with pytest.raises(ReorderError, match=r"segment 40\b.*\(code -1\)"):
+                st.invert(data, off, [p[1] for p in pairs])
+            with pytest.raises(ReorderError, match="code -4"):
+                st.download()
+        pairs[40] = good[40]   # the later one alone
+        with pytest.raises(ReorderError, match=r"segment 8000\b.*\(code -1\)"):
+            st.invert(data, off, [p[1] for p in pairs])
+        with pytest.raises(ReorderError, match="code -4"):
+            st.download()
+        st.invert(data, off, [p[1] for p in good])   # the context works on
+        _same(st.download(), good, "after the refusals")
+
+
 def test_refusals():
     from spring_amd import _lib
     from spring_amd.bwt import BwtStage
