@@ -148,6 +148,9 @@ typedef struct {
                                   reads), bit 1 = the table was written in one pass (clear: memset, merge and insert passes) */
   uint64_t strand_filter;      /* 1: the chain phase ran the presence-table sweep (opts.strand_filter) */
   uint64_t strand_filter_dropped; /* keys the presence table does not hold because their bucket was full (last dictionary built) */
+  uint64_t strand_filter_build;   /* how the last dictionary build made the presence table: 0 = no table, 1 = memset, then every
+                                     key through the insert pass (opts.dict_build_mode = 1), 2 = every bucket written once with
+                                     the keys that are their own canonical form in place, the rest through the insert pass */
 } spring_reorder_stats;
 
 void spring_reorder_default_opts(spring_reorder_opts *o);
@@ -328,6 +331,11 @@ int spring_reorder_emit_dna(spring_reorder_ctx *ctx, int32_t tid, uint8_t *dst, 
  * ids are concatenated into bin_ids (capacity ids_cap). */
 int spring_reorder_dict_lookup(spring_reorder_ctx *ctx, int32_t which, const uint64_t *keys, uint32_t nkeys,
                                uint32_t *bin_size, uint32_t *bin_ids, size_t ids_cap);
+
+/* Test hook: the strand-symmetric presence table of the last dictionary build (opts.strand_filter; valid from build_dict
+ * on): *lgb = lg2 of its buckets, and its 16 << *lgb bytes -- four 32-bit slot words a bucket, fingerprint << 4 | flags,
+ * 0 = empty -- copied to out (capacity cap bytes).  out = NULL: only *lgb.  E_STATE where the build made no table. */
+int spring_reorder_presence_table(spring_reorder_ctx *ctx, void *out, size_t cap, int32_t *lgb);
 
 /* Test hook: limb array + lengths as the unpack kernel produced them. */
 int spring_reorder_download_reads(spring_reorder_ctx *ctx, uint64_t *limbs /* n*W */, uint16_t *len);

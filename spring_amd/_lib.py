@@ -15,7 +15,7 @@ EXPORTS = [
     "spring_mg_rccl_unique_id", "spring_mg_comm_create_rccl", "spring_mg_comm_create_host", "spring_mg_comm_destroy",
     "spring_reorder_mg_run",
     "spring_reorder_get_stats", "spring_reorder_download", "spring_reorder_tid_split", "spring_reorder_emit_dna",
-    "spring_reorder_dict_lookup", "spring_reorder_download_reads", "spring_synth_dna_bytes",
+    "spring_reorder_dict_lookup", "spring_reorder_presence_table", "spring_reorder_download_reads", "spring_synth_dna_bytes",
     "spring_reorder_load_fastq", "spring_reorder_fastq_N",
     "spring_order_invert_se", "spring_order_invert_pe", "spring_order_correct", "spring_order_pe_encode",
     "spring_fastq_reorder",
@@ -221,7 +221,8 @@ class Stats(C.Structure):
                    ("ms_search_busy", C.c_double),
                    ("sort_prefix_bits", C.c_uint64), ("sort_repaired_runs", C.c_uint64), ("sort_full_sorts", C.c_uint64),
                    ("sort_long_runs", C.c_uint64), ("sort_list_overflows", C.c_uint64), ("dict_build_path", C.c_uint64),
-                   ("strand_filter", C.c_uint64), ("strand_filter_dropped", C.c_uint64)])
+                   ("strand_filter", C.c_uint64), ("strand_filter_dropped", C.c_uint64),
+                   ("strand_filter_build", C.c_uint64)])
 
     def asdict(self):
         d = {}
@@ -282,6 +283,7 @@ def lib():
     L.spring_reorder_tid_split.argtypes = [vp, vp, vp]
     L.spring_reorder_emit_dna.argtypes = [vp, C.c_int32, u8p, C.c_size_t, C.POINTER(C.c_size_t)]
     L.spring_reorder_dict_lookup.argtypes = [vp, C.c_int32, vp, C.c_uint32, vp, vp, C.c_size_t]
+    L.spring_reorder_presence_table.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_int32)]
     L.spring_reorder_download_reads.argtypes = [vp, vp, vp]
     L.spring_reorder_load_fastq.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.POINTER(FastqInfo)]
     L.spring_reorder_fastq_N.argtypes = [vp, C.c_int32, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.POINTER(C.c_uint32)]

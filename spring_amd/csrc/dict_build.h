@@ -35,12 +35,21 @@ void launch_tab_overflow_blocks(hipStream_t st, const uint64_t *h0, uint32_t nk0
 void launch_tab_overflow_pairs(hipStream_t st, const uint64_t *h0, uint32_t nk0, const uint64_t *h1, DictBuild d0,
                                DictBuild d1, uint32_t *fpt, int bshift, const uint32_t *ovf, uint32_t novf);
 
-// ---- the strand-symmetric presence table (strand_filter.h): 2^lgb buckets of four 32-bit slots at pres, zeroed by the
-// caller.  Every unique key of both dictionaries (h0 / h1: their sorted unique hashes, windows of wl bases) is entered
-// under its canonical form; drops: PRES_DROP_CTRS zeroed counters whose sum is the number of keys that met a full bucket.
+// ---- the strand-symmetric presence table (strand_filter.h): 2^lgb buckets of four 32-bit slots at pres.  Every unique
+// key of both dictionaries (h0 / h1: their sorted unique hashes, windows of wl bases) is entered under its canonical
+// form; drops: PRES_DROP_CTRS zeroed counters whose sum is the number of keys that met a full bucket.
+//   launch_pres_insert  the table zeroed by the caller (skip_self_canonical = false), or written by launch_pres_write
+//                       earlier on the same stream (true: only the keys filed under their reverse complement are entered)
+//   launch_pres_write   writes EVERY bucket of the table, no memset before it, with the keys that are their own canonical
+//                       form in place (they come in bucket order).  part: 2 * (pres_write_blocks(lgb) + 1) words of scratch
 constexpr uint32_t PRES_DROP_CTRS = 1024;
+constexpr int PRES_WRITE_LG = 10;  // buckets per workgroup of the writer: 2^10 = a 16 KB image in LDS
+inline int pres_write_lg(int lgb) { return lgb < PRES_WRITE_LG ? lgb : PRES_WRITE_LG; }
+inline uint32_t pres_write_blocks(int lgb) { return 1u << (lgb - pres_write_lg(lgb)); }
 void launch_pres_insert(hipStream_t st, const uint64_t *h0, uint32_t nk0, const uint64_t *h1, uint32_t nk1, int wl, uint32_t *pres,
-                        int lgb, uint32_t *drops);
+                        int lgb, uint32_t *drops, bool skip_self_canonical);
+void launch_pres_write(hipStream_t st, const uint64_t *h0, uint32_t nk0, const uint64_t *h1, uint32_t nk1, int wl, uint4 *pres,
+                       int lgb, uint32_t *part, uint32_t *drops);
 
 }  // namespace sr
 

@@ -7,7 +7,9 @@
 //   k_tab_write          one workgroup per block of buckets builds the block's image in LDS and stores it in full
 //                        lines -- no memset of the table, no merged list of the two dictionaries (merge_by_hash)
 //   k_tab_overflow_blocks / _pairs  the pairs past the fourth of a bucket claim a free slot further on (CAS), as before
-//   k_pres_insert        the strand-symmetric presence table (strand_filter.h): one slot per canonical window
+//   k_pres_write         the strand-symmetric presence table (strand_filter.h), the keys that are their own canonical
+//                        form: they arrive in bucket order, so the table is written front to back like the main one
+//   k_pres_insert        ... and the keys filed under their reverse complement: one claim-or-OR per key, anywhere
 // The table they produce answers every lookup as the one k_tab_insert builds (reorder_kernels.hip): same tags, same
 // payloads, the same pairs in the home buckets.
 #include <hip/hip_runtime.h>
@@ -133,7 +135,7 @@ __global__ void k_tab_partition(const uint64_t *__restrict__ h0, uint32_t nk0, c
   uint32_t lo = 0, hi = nk;
   if (j == nblk) {
     lo = nk;
-  } else {
+  } else if (j != 0u) {  // (block 0 starts at key 0; a table of one bucket has bshift = 64 and no other block)
     const uint64_t bound = ((uint64_t)j << lg) << bshift;  // the smallest hash of bucket j << lg
     while (lo < hi) {
       const uint32_t mid = lo + (hi - lo) / 2;
@@ -331,21 +333,75 @@ void launch_tab_overflow_pairs(hipStream_t st, const uint64_t *h0, uint32_t nk0,
 // from, so every key of the main table is covered).  The slot of canon(key) is claimed with one CAS that already carries
 // the key's flag; a thread that finds the fingerprint there ORs its flag in.  Keys that meet a full bucket are counted per
 // workgroup in LDS and added to one of PRES_DROP_CTRS counters: no same-address atomic per dropped key.
+//
+// k_pres_write: the keys that are their own canonical form, K <= rc(K) -- half of the others and every palindrome.  Such
+// a key is filed under mix64(canon(K)) = mix64(K), the very hash its array is sorted by, so the keys of the buckets
+// [j << lg, (j + 1) << lg) are one interval of each array (k_tab_partition with the shift 64 - lgb).  One workgroup per
+// block of 2^lg buckets: it zeroes the block's image in LDS, enters its keys there by k_pres_insert's rule -- slots 0..3
+// in order, claim an empty one with a CAS that carries the flags, or OR them into the slot that has the fingerprint,
+// else count a drop -- and stores the image in 16-byte pieces.  Every bucket of the table is written, by the workgroups
+// without keys too: nothing zeroes the table before this kernel.  The loop strides over however many keys the block has
+// (a capped table: all of them in a few buckets).  The keys with rc(K) < K are read and passed over: k_pres_insert's.
+constexpr uint32_t PRES_WRITE_THREADS = 256;
+__global__ __launch_bounds__(PRES_WRITE_THREADS) void k_pres_write(const uint64_t *__restrict__ h0, const uint64_t *__restrict__ h1,
+                                                                   const uint32_t *__restrict__ part, uint32_t nblk, int wl,
+                                                                   uint4 *__restrict__ pres, int lgb, int lg,
+                                                                   uint32_t *__restrict__ drops) {
+  __shared__ uint4 img[1u << PRES_WRITE_LG];
+  __shared__ uint32_t s_drop;
+  const uint32_t nbk = 1u << lg, bmask = nbk - 1u, blk = blockIdx.x;
+  for (uint32_t k = threadIdx.x; k < nbk; k += PRES_WRITE_THREADS) img[k] = make_uint4(0u, 0u, 0u, 0u);
+  if (threadIdx.x == 0) s_drop = 0u;
+  const uint32_t a0 = part[blk], a1 = part[(uint64_t)nblk + 1 + blk];
+  const uint32_t c0 = part[blk + 1] - a0, c1 = part[(uint64_t)nblk + 2 + blk] - a1;
+  const uint32_t ntot = c0 + c1;
+  __syncthreads();
+  uint32_t *imgw = reinterpret_cast<uint32_t *>(img);
+  for (uint32_t t = threadIdx.x; t < ntot; t += PRES_WRITE_THREADS) {
+    const int l = t >= c0 ? 1 : 0;
+    const uint64_t h = l ? h1[a1 + (t - c0)] : h0[a0 + t];
+    uint32_t flags;
+    const uint64_t cw = sf::canon_and_flags(db_unmix64(h), wl, l, flags);
+    if (!(flags & (1u << l))) continue;  // rc(K) < K
+    const uint64_t hc = sf::mix64(cw);   // (= h: the key is its canonical form)
+    const uint32_t fp = sf::fp_of(hc), word = (fp << 4) | flags;
+    uint32_t *bk = imgw + 4u * (sf::bucket_of(hc, lgb) & bmask);
+    bool placed = false;
+    for (int sl = 0; sl < 4 && !placed; sl++) {
+      const uint32_t old = atomicCAS(bk + sl, 0u, word);
+      if (old == 0u) placed = true;
+      else if ((old >> 4) == fp) {
+        if ((old & word & 15u) != (word & 15u)) atomicOr(bk + sl, word & 15u);
+        placed = true;
+      }
+    }
+    if (!placed) atomicAdd(&s_drop, 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && s_drop) atomicAdd(drops + (blk & (PRES_DROP_CTRS - 1u)), s_drop);
+  uint4 *__restrict__ out = pres + ((uint64_t)blk << lg);
+  for (uint32_t k = threadIdx.x; k < nbk; k += PRES_WRITE_THREADS) out[k] = img[k];
+}
+// skip_self: the keys that are their own canonical form (a palindrome is) are in the table already (k_pres_write, a
+// kernel boundary earlier): their threads leave before they touch it.
 __global__ __launch_bounds__(256) void k_pres_insert(const uint64_t *__restrict__ h0, uint32_t nk0, const uint64_t *__restrict__ h1,
                                                      uint32_t nk1, int wl, uint32_t *__restrict__ pres, int lgb,
-                                                     uint32_t *__restrict__ drops) {
+                                                     uint32_t *__restrict__ drops, int skip_self) {
   __shared__ uint32_t s_drop;
   if (threadIdx.x == 0) s_drop = 0u;
   __syncthreads();
   const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < (uint64_t)nk0 + nk1) {
+  bool mine = t < (uint64_t)nk0 + nk1;
+  if (mine) {
     const int l = t >= nk0 ? 1 : 0;
     const uint64_t key = db_unmix64(l ? h1[t - nk0] : h0[t]);
     uint32_t flags;
-    const uint64_t hc = sf::mix64(sf::canon_and_flags(key, wl, l, flags));
+    const uint64_t cw = sf::canon_and_flags(key, wl, l, flags);
+    if (skip_self && (flags & (1u << l))) mine = false;  // (bit l: key <= rc(key))
+    const uint64_t hc = sf::mix64(cw);
     const uint32_t fp = sf::fp_of(hc), word = (fp << 4) | flags;
     uint32_t *bk = pres + 4ull * sf::bucket_of(hc, lgb);
-    bool placed = false;
+    bool placed = !mine;
     for (int sl = 0; sl < 4 && !placed; sl++) {
       uint32_t old = __hip_atomic_load(bk + sl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (old == 0u) old = atomicCAS(bk + sl, 0u, word);
@@ -361,10 +417,19 @@ __global__ __launch_bounds__(256) void k_pres_insert(const uint64_t *__restrict_
   if (threadIdx.x == 0 && s_drop) atomicAdd(drops + (blockIdx.x & (PRES_DROP_CTRS - 1u)), s_drop);
 }
 void launch_pres_insert(hipStream_t st, const uint64_t *h0, uint32_t nk0, const uint64_t *h1, uint32_t nk1, int wl, uint32_t *pres,
-                        int lgb, uint32_t *drops) {
+                        int lgb, uint32_t *drops, bool skip_self_canonical) {
   const uint64_t nt = (uint64_t)nk0 + nk1;
   if (!nt) return;
-  hipLaunchKernelGGL(k_pres_insert, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, h0, nk0, h1, nk1, wl, pres, lgb, drops);
+  hipLaunchKernelGGL(k_pres_insert, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, h0, nk0, h1, nk1, wl, pres, lgb, drops,
+                     skip_self_canonical ? 1 : 0);
+}
+void launch_pres_write(hipStream_t st, const uint64_t *h0, uint32_t nk0, const uint64_t *h1, uint32_t nk1, int wl, uint4 *pres,
+                       int lgb, uint32_t *part, uint32_t *drops) {
+  const int lg = pres_write_lg(lgb);
+  const uint32_t nblk = pres_write_blocks(lgb);
+  const uint64_t nt = 2ull * ((uint64_t)nblk + 1);
+  hipLaunchKernelGGL(k_tab_partition, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, h0, nk0, h1, nk1, 64 - lgb, lg, nblk, part);
+  hipLaunchKernelGGL(k_pres_write, dim3(nblk), dim3(PRES_WRITE_THREADS), 0, st, h0, h1, part, nblk, wl, pres, lgb, lg, drops);
 }
 
 }  // namespace sr

@@ -1082,6 +1082,28 @@ static TabView tab_view(const spring_reorder_ctx *ctx) {
 static unsigned sort_prefix_auto(uint64_t m) { return m <= (1ull << 29) ? 40u : 48u; }
 
 static bool strand_filter_wanted(const spring_reorder_ctx *ctx);
+
+// ---- the strand-symmetric presence table (strand_filter.h; opts.strand_filter), only where the chain phase will read it.
+// Size: at least one bucket per key, the next power of two -- between 0.5 and 1 keys per four-slot bucket (a load of
+// 0.125 .. 0.25; fewer where a window and its reverse complement are both keys: they share a slot).  Keys fall into
+// buckets like a Poisson variable of that mean: 0.18 % .. 1.9 % of the buckets are full, and a full bucket costs a
+// lookup nothing but its answer (the main table is asked as before).  16 bytes a bucket: 4.3 GB for the 194 M keys of
+// 100 M reads of 150 bases (0.72 keys per bucket: 0.6 % full), against the 17 GB of the main table.
+// presence_alloc allocates ctx->pres for nm keys and returns lg2 of its buckets; ctx->pres stays null where it does not fit.
+static bool presence_wanted(const spring_reorder_ctx *ctx, uint64_t nm) { return nm && nm < 0xffffffffull && strand_filter_wanted(ctx); }
+static int presence_alloc(spring_reorder_ctx *ctx, uint64_t nm, bool dbg) {
+  int lgb = 0;
+  while (lgb < 32 && (1ull << lgb) < nm) lgb++;
+  if (ctx->o.strand_filter > 0) lgb = std::min(lgb, ctx->o.strand_filter);
+  // The table only saves work: a pool that fits without it must not fail for it.  No room: the chain phase runs without
+  // the sweep (setup_chains sees no table; stats.strand_filter = 0).
+  if (ctx->dmalloc((void **)&ctx->pres, (size_t)16 << lgb)) {
+    (void)hipGetLastError();
+    ctx->pres = nullptr;
+    if (dbg) fprintf(stderr, "[dict] presence table: no room for 2^%d buckets, running without\n", lgb);
+  }
+  return lgb;
+}
 int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
   double t_last = now_ms();
   if (!ctx) return fail(SPRING_REORDER_E_ARG, "ctx is NULL");
@@ -1091,6 +1113,8 @@ int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
   hipStream_t st = ctx->st;
   const uint32_t n = ctx->n;
   HIPCHK(hipEventRecord(ctx->ev[2], st));
+  ctx->pres = nullptr; ctx->pres_lgb = 0;
+  ctx->stats.strand_filter = 0; ctx->stats.strand_filter_dropped = 0; ctx->stats.strand_filter_build = 0;
   uint64_t *uhash[2] = {nullptr, nullptr};          // sorted unique mix64(key) per dictionary
   uint32_t *ustart[2] = {nullptr, nullptr}, *ucount[2] = {nullptr, nullptr};
   // pools of one read length: every read is in both dictionaries, and one pass over the reads serves both
@@ -1380,41 +1404,34 @@ int spring_reorder_build_dict(spring_reorder_ctx *ctx) {
     ctx->dfree(mv0); ctx->dfree(mh); ctx->dfree(mv); ctx->dfree(d_tmp);
     ctx->dfree(bk_in); ctx->dfree(bk_out); ctx->dfree(tp_in); ctx->dfree(tp_out); ctx->dfree(d_tmp2); ctx->dfree(d_marked); ctx->dfree(d_ovf);
   }
-  // ---- the strand-symmetric presence table (strand_filter.h; opts.strand_filter), only where the chain phase will read it.
-  // Size: at least one bucket per key, the next power of two -- between 0.5 and 1 keys per four-slot bucket (a load of
-  // 0.125 .. 0.25; fewer where a window and its reverse complement are both keys: they share a slot).  Keys fall into
-  // buckets like a Poisson variable of that mean: 0.18 % .. 1.9 % of the buckets are full, and a full bucket costs a
-  // lookup nothing but its answer (the main table is asked as before).  16 bytes a bucket: 4.3 GB for the 194 M keys of
-  // 100 M reads of 150 bases (0.72 keys per bucket: 0.6 % full), against the 17 GB of the main table.
-  ctx->pres = nullptr; ctx->pres_lgb = 0;
-  ctx->stats.strand_filter = 0; ctx->stats.strand_filter_dropped = 0;
+  // ---- the presence table, behind the main table on the one stream.  Beside the one-pass table it is written once too
+  // (DESIGN.md section 4): k_pres_write stores every bucket, the keys that are their own canonical form in place -- they
+  // come in bucket order -- and k_pres_insert enters the others where they fall.  opts.dict_build_mode = 1 (and whatever
+  // else keeps the main table's insert passes): memset, then every key through k_pres_insert.
   int lgb = 0;
-  if (nm && nm < 0xffffffffull && strand_filter_wanted(ctx)) {
-    while (lgb < 32 && (1ull << lgb) < nm) lgb++;
-    if (ctx->o.strand_filter > 0) lgb = std::min(lgb, ctx->o.strand_filter);
-    // The table only saves work: a pool that fits without it must not fail for it.  No room: the chain phase runs without
-    // the sweep (setup_chains sees no table; stats.strand_filter = 0).
-    if (ctx->dmalloc((void **)&ctx->pres, (size_t)16 << lgb)) {
-      (void)hipGetLastError();
-      ctx->pres = nullptr;
-      if (dbg) fprintf(stderr, "[dict] presence table: no room for 2^%d buckets, running without\n", lgb);
-    }
-  }
+  if (presence_wanted(ctx, nm)) lgb = presence_alloc(ctx, nm, dbg);
   if (ctx->pres) {
-    uint32_t *d_drops = nullptr;
+    const int wl = ctx->dict[0].end - ctx->dict[0].start + 1;
+    uint32_t *d_drops = nullptr, *d_part = nullptr;
     std::vector<uint32_t> h_drops(PRES_DROP_CTRS);
     DMALLOC(d_drops, PRES_DROP_CTRS * 4);
-    HIPCHK(hipMemsetAsync(ctx->pres, 0, (size_t)16 << lgb, st));
     HIPCHK(hipMemsetAsync(d_drops, 0, PRES_DROP_CTRS * 4, st));
-    launch_pres_insert(st, uhash[0], (uint32_t)nk0, uhash[1], (uint32_t)nk1, ctx->dict[0].end - ctx->dict[0].start + 1,
-                       reinterpret_cast<uint32_t *>(ctx->pres), lgb, d_drops);
+    if (one_pass) {
+      DMALLOC(d_part, 2 * ((size_t)pres_write_blocks(lgb) + 1) * 4);
+      launch_pres_write(st, uhash[0], (uint32_t)nk0, uhash[1], (uint32_t)nk1, wl, ctx->pres, lgb, d_part, d_drops);
+    } else {
+      HIPCHK(hipMemsetAsync(ctx->pres, 0, (size_t)16 << lgb, st));
+    }
+    launch_pres_insert(st, uhash[0], (uint32_t)nk0, uhash[1], (uint32_t)nk1, wl, reinterpret_cast<uint32_t *>(ctx->pres), lgb, d_drops,
+                       one_pass);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h_drops.data(), d_drops, PRES_DROP_CTRS * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     for (uint32_t v : h_drops) ctx->stats.strand_filter_dropped += v;
     ctx->pres_lgb = lgb;
-    ctx->dfree(d_drops);
-    if (dbg) fprintf(stderr, "[dict] presence table: 2^%d buckets, %llu of %llu keys dropped\n", lgb,
+    ctx->stats.strand_filter_build = one_pass ? 2 : 1;
+    ctx->dfree(d_drops); ctx->dfree(d_part);
+    if (dbg) fprintf(stderr, "[dict] presence table: 2^%d buckets%s, %llu of %llu keys dropped\n", lgb, one_pass ? " written once" : "",
                      (unsigned long long)ctx->stats.strand_filter_dropped, (unsigned long long)nm);
     DBG_T("presence table");
   }
@@ -1460,6 +1477,19 @@ int spring_reorder_dict_lookup(spring_reorder_ctx *ctx, int32_t which, const uin
     memcpy(bin_ids + o, hids.data() + hs[i], (size_t)hc[i] * 4);
     o += hc[i];
   }
+  return 0;
+}
+
+int spring_reorder_presence_table(spring_reorder_ctx *ctx, void *out, size_t cap, int32_t *lgb) {
+  if (!ctx || ctx->stage < ST_DICT) return fail(SPRING_REORDER_E_STATE, "presence_table: build_dict first");
+  if (!ctx->pres) return fail(SPRING_REORDER_E_STATE, "presence_table: this build made no presence table");
+  const size_t nb = (size_t)16 << ctx->pres_lgb;
+  if (lgb) *lgb = ctx->pres_lgb;
+  if (!out) return 0;
+  if (cap < nb) return fail(SPRING_REORDER_E_ARG, "presence_table: the table has %zu bytes, the buffer %zu", nb, cap);
+  HIPCHK(hipSetDevice(ctx->dev));
+  HIPCHK(hipMemcpyAsync(out, ctx->pres, nb, hipMemcpyDeviceToHost, ctx->st));
+  HIPCHK(hipStreamSynchronize(ctx->st));
   return 0;
 }
 

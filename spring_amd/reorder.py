@@ -230,6 +230,15 @@ class ReorderStage:
                                                 ids.ctypes.data, len(ids)))
         return sizes[:len(keys)], ids
 
+    def presence_table(self):
+        """-> (lgb, slots): the strand-symmetric presence table of the last build_dict as a (2**lgb, 4) array of slot
+        words (fingerprint << 4 | flags, 0 = empty).  ReorderError where the build made none."""
+        lgb = C.c_int32(0)
+        _chk(self._L.spring_reorder_presence_table(self._h, None, 0, C.byref(lgb)))
+        slots = np.zeros((1 << lgb.value, 4), np.uint32)
+        _chk(self._L.spring_reorder_presence_table(self._h, slots.ctypes.data, slots.nbytes, C.byref(lgb)))
+        return lgb.value, slots
+
     def download_reads(self):
         W = (2 * self.max_readlen - 1) // 64 + 1
         limbs = np.zeros((max(self.n, 1), W), np.uint64)
