@@ -62,9 +62,11 @@ GZIP_EXPORTS = [
 BWT_EXPORTS = [
     "spring_bwt_create", "spring_bwt_destroy", "spring_bwt_set_block_bytes", "spring_bwt_set_workspace_bytes",
     "spring_bwt_workspace_need", "spring_bwt_from_host", "spring_bwt_from_streams", "spring_bwt_download",
-    "spring_bwt_segments", "spring_bwt_get_info", "spring_bwt_encode_inplace",
+    "spring_bwt_segments", "spring_bwt_get_info", "spring_bwt_encode_inplace", "spring_bwt_set_run_keys",
+    "spring_bwt_from_qualid", "spring_bwt_round_entries",
 ]
 BWT_MAX_INDEXES = 256  # SPRING_BWT_MAX_INDEXES
+BWT_SRC_QUALITY, BWT_SRC_ID = -2, -3  # SPRING_BWT_SRC_QUALITY, SPRING_BWT_SRC_ID
 
 # include/spring_unbwt.h: a list of its own as well
 UNBWT_EXPORTS = [
@@ -171,7 +173,7 @@ class GzipInfo(C.Structure):
 class BwtInfo(C.Structure):
     _fields_ = ([(k, C.c_uint64) for k in ("num_segments", "bytes", "max_segment", "sub_batches", "rounds",
                                            "rounds_total", "workspace_bytes")]
-                + [("ms_device", C.c_double), ("ms_pass", C.c_double * 5)])
+                + [("ms_device", C.c_double), ("ms_pass", C.c_double * 5), ("run_positions", C.c_uint64)])
 
     def asdict(self):
         d = {}
@@ -381,6 +383,9 @@ def lib():
     L.spring_bwt_segments.argtypes = [vp, vp, vp, vp]
     L.spring_bwt_get_info.argtypes = [vp, C.POINTER(BwtInfo)]
     L.spring_bwt_encode_inplace.argtypes = [vp, u8p, C.c_int32, vp, vp]
+    L.spring_bwt_set_run_keys.argtypes = [vp, C.c_int32, C.c_uint32]
+    L.spring_bwt_round_entries.argtypes = [vp, vp, C.c_uint64]
+    L.spring_bwt_from_qualid.argtypes = [vp, vp, C.c_int32, C.c_uint64, C.POINTER(BwtInfo)]
     L.spring_unbwt_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_unbwt_destroy.argtypes = [vp]
     L.spring_unbwt_destroy.restype = None

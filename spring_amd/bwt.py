@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .qualid import KIND, QualIdStage
 from .reorder import ReorderError
 from .streams import STREAM_ID, StreamsStage
 
@@ -23,8 +24,8 @@ def workspace_need(nbytes, segments=1):
 
 class BwtStage:
     """transform(): the Burrows-Wheeler transform, primary index and libbsc's secondary indexes of every segment of a
-    batch, on the device.  The batch is host bytes with offsets, or the (stream, block) slices of a StreamsStage, read
-    in place in HBM.  download() / segments() fetch the result."""
+    batch, on the device.  The batch is host bytes with offsets, or the (stream, block) slices of a StreamsStage or the
+    quality / id blocks of a QualIdStage, read in place in HBM.  download() / segments() fetch the result."""
 
     def __init__(self, device: int = -1):
         self._L = _lib.lib()
@@ -57,13 +58,23 @@ class BwtStage:
         """The device workspace a sub-batch may use (0: from the free HBM)."""
         _chk(self._L.spring_bwt_set_workspace_bytes(self._h, workspace_bytes))
 
-    def transform(self, src, seg_off=None, streams=None):
+    def set_run_keys(self, on, cap_bits=0):
+        """Run-aware first keys for the calls that follow (default: off): same results, fewer rounds on content with
+        few symbols and long runs.  cap_bits: 0 (the layout's own width) or 2 .. that width."""
+        _chk(self._L.spring_bwt_set_run_keys(self._h, int(bool(on)), cap_bits))
+
+    def transform(self, src, seg_off=None, streams=None, kind="quality", block_bytes=0):
         """src: a StreamsStage holding a run; streams: the streams to take (ids, file names or short names; None: all
-        nine).  Or bytes / a uint8 array; seg_off: num_segments + 1 offsets from 0 to len(src) that do not decrease
-        (None: one segment).  -> info."""
+        nine).  Or a QualIdStage holding a result; kind: "quality" or "id"; block_bytes: the cut inside a block (0: the
+        64 MiB SPRING passes).  Or bytes / a uint8 array; seg_off: num_segments + 1 offsets from 0 to len(src) that do
+        not decrease (None: one segment).  -> info."""
         info = _lib.BwtInfo()
         self.info = None
-        if isinstance(src, StreamsStage):
+        if isinstance(src, QualIdStage):
+            if seg_off is not None or streams is not None:
+                raise ValueError("seg_off and streams are not for a QualIdStage: it is cut by its blocks and block_bytes")
+            _chk(self._L.spring_bwt_from_qualid(self._h, src._h, KIND.get(kind, kind), block_bytes, C.byref(info)))
+        elif isinstance(src, StreamsStage):
             if seg_off is not None:
                 raise ValueError("seg_off is for host buffers; a StreamsStage is cut by its blocks and block_bytes")
             ids = range(_lib.STREAMS_NUM) if streams is None else [s if isinstance(s, int) else STREAM_ID[s] for s in streams]
@@ -101,13 +112,22 @@ class BwtStage:
         return dict(bwt=buf[:n].tobytes(), seg_off=off, primary=primary[:S], num_indexes=num[:S], indexes=idx[:S])
 
     def segments(self):
-        """-> (stream id (-1: host input), block, cut) of every segment: three arrays."""
+        """-> (stream id (-1: host input, -2 / -3: quality / id blocks), block, cut) of every segment: three arrays."""
         if self.info is None:
             _chk(self._L.spring_bwt_segments(self._h, None, None, None))
         S = self.info["num_segments"]
         st, bl, cu = np.zeros(max(S, 1), np.int32), np.zeros(max(S, 1), np.uint32), np.zeros(max(S, 1), np.uint32)
         _chk(self._L.spring_bwt_segments(self._h, st.ctypes.data, bl.ctypes.data, cu.ctypes.data))
         return st[:S], bl[:S], cu[:S]
+
+    def round_entries(self):
+        """-> the entries every sort round of the last call sorted (round 0: every position), summed over the
+        sub-batches: uint64 array of info["rounds"] entries."""
+        if self.info is None:
+            _chk(self._L.spring_bwt_round_entries(self._h, None, 0))
+        e = np.zeros(max(self.info["rounds"], 1), np.uint64)
+        _chk(self._L.spring_bwt_round_entries(self._h, e.ctypes.data, len(e)))
+        return e[:self.info["rounds"]]
 
     def encode_inplace(self, T):
         """bsc_bwt_encode's contract on a writable uint8 array (None or empty: n = 0): T is transformed in place.

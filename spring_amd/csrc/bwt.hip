@@ -10,6 +10,10 @@
 // A group occupies consecutive slots and its rank is its first slot, so a re-sorted group falls back into its own
 // slots and the ranks of every other position stay what they are (Larsson & Sadakane).  Every loop on the device has a
 // static bound; the round loop on the host carries bwt::max_rounds.
+//
+// With run-aware keys on (spring_bwt_set_run_keys) the first key also carries, for a position inside a run of one byte,
+// on which side of the run's byte the byte behind the run lies and how long the rest of the run is, and the doubling
+// rounds of such a position look behind its run (hop) instead of into it.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -19,6 +23,7 @@
 
 #include "bwt_internal.h"
 #include "bwt_plan.h"
+#include "fastq_out_internal.h"
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_bwt.h"
@@ -36,6 +41,7 @@ using sr::fail;
 namespace {
 
 constexpr uint64_t DEFAULT_BLOCK_BYTES = 25ull * 1024 * 1024;   // bsc.cpp:80
+constexpr uint64_t QUALID_BLOCK_BYTES = 64ull * 1024 * 1024;    // "-b64", what BSC_str_array_compress passes
 constexpr uint64_t SORT_FIXED_BYTES = 8ull << 20;               // the sort's tables that do not grow with the input
 
 struct DBuf {
@@ -77,18 +83,12 @@ __device__ __forceinline__ uint32_t seg_of(const Sub &G, uint32_t p) {
 }
 
 // ------------------------------------------------------------------ first keys
-// One position per lane.  Away from the segment's ends the bytes come from the two aligned 8-byte words around the
-// position (both inside the segment); within 16 bytes of an end, byte by byte and never past it.
-__global__ __launch_bounds__(256) void k_first_keys(Sub G, bwt::KeyLayout K, uint64_t *__restrict__ key,
-                                                    uint32_t *__restrict__ val, uint32_t *__restrict__ uslot) {
-  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
-  if (p >= G.m) return;
-  const uint32_t s = seg_of(G, p);
-  const uint64_t so = G.off[G.first + s] - G.base, len = G.off[G.first + s + 1] - G.off[G.first + s];
-  const uint64_t i = p - so, rem = len - i;
-  const uint8_t *a = reinterpret_cast<const uint8_t *>(G.src[G.first + s]) + i;
-  const uint32_t valid = rem < (uint64_t)K.key_bytes ? (uint32_t)rem : (uint32_t)K.key_bytes;
-  uint64_t be = 0;   // the next eight bytes, the first one on top; zero behind the segment's end
+// The next eight bytes at a (byte i of its segment, rem bytes left), the first one on top; only the first `valid` (at
+// most 7) of them count, and behind the segment's end they are zero.  Away from the segment's ends the bytes come from
+// the two aligned 8-byte words around the position (both inside the segment); within 16 bytes of an end, byte by byte
+// and never past it.
+__device__ __forceinline__ uint64_t next_bytes(const uint8_t *a, uint64_t i, uint64_t rem, uint32_t valid) {
+  uint64_t be = 0;
   if (i >= 8 && rem >= 16) {
     const uint64_t addr = reinterpret_cast<uint64_t>(a);
     const uint64_t *w = reinterpret_cast<const uint64_t *>(addr & ~7ull);
@@ -100,23 +100,97 @@ __global__ __launch_bounds__(256) void k_first_keys(Sub G, bwt::KeyLayout K, uin
     for (uint32_t k = 0; k < 7; k++)
       if (k < valid) be |= (uint64_t)a[k] << (56 - 8 * k);
   }
+  return be;
+}
+
+// One position per lane.
+__global__ __launch_bounds__(256) void k_first_keys(Sub G, bwt::KeyLayout K, uint64_t *__restrict__ key,
+                                                    uint32_t *__restrict__ val, uint32_t *__restrict__ uslot) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= G.m) return;
+  const uint32_t s = seg_of(G, p);
+  const uint64_t so = G.off[G.first + s] - G.base, len = G.off[G.first + s + 1] - G.off[G.first + s];
+  const uint64_t i = p - so, rem = len - i;
+  const uint8_t *a = reinterpret_cast<const uint8_t *>(G.src[G.first + s]) + i;
+  const uint32_t valid = rem < (uint64_t)K.key_bytes ? (uint32_t)rem : (uint32_t)K.key_bytes;
+  const uint64_t be = next_bytes(a, i, rem, valid);
   const uint64_t bytes = be >> (64 - 8 * K.key_bytes);
   key[p] = ((uint64_t)s << (8 * K.key_bytes + bwt::VALID_BITS)) | (bytes << bwt::VALID_BITS) | valid;
   val[p] = p;
   uslot[p] = p;
 }
 
+// ------------------------------------------------------------------ run-aware first keys
+// Run ends, mirrored so that a forward inclusive max-scan serves: flag[m - 1 - p] = m - 1 - p where p is the last
+// position of its run of equal bytes or of its segment, else 0 (the neutral element; slot 0 is position m - 1, which
+// ends its segment).  After the scan, word m - 1 - p holds m - 1 - e for the first such e >= p.
+__global__ __launch_bounds__(256) void k_run_ends(Sub G, uint32_t *__restrict__ flag) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= G.m) return;
+  const uint32_t s = seg_of(G, p);
+  const uint64_t so = G.off[G.first + s] - G.base, len = G.off[G.first + s + 1] - G.off[G.first + s];
+  const uint64_t i = p - so;
+  const uint8_t *a = reinterpret_cast<const uint8_t *>(G.src[G.first + s]) + i;
+  const bool last = i + 1 == len || a[1] != a[0];
+  const uint32_t j = G.m - 1 - p;
+  flag[j] = last ? j : 0;
+}
+
+// The first key of k_first_keys with two more fields below `valid`: side (1 bit) and mag (run_bits), both zero unless
+// the next key_bytes bytes exist and are equal -- position p lies in a run of its byte c with L >= key_bytes bytes left
+// inside the segment.  d = the byte behind the run:  the run ends the segment, or d < c: side 0, mag = min(L, cap);
+// d > c: side 1, mag = cap - min(L, cap).  hop[p] = L where key_bytes <= L < cap (the positions that tie with p have
+// the same c, side and L, so what tells them apart starts L bytes on), else 0.  rend: the scan over k_run_ends.
+__global__ __launch_bounds__(256) void k_first_keys_runs(Sub G, bwt::RunKeyLayout K, uint32_t cap,
+                                                         const uint32_t *__restrict__ rend, uint64_t *__restrict__ key,
+                                                         uint32_t *__restrict__ val, uint32_t *__restrict__ uslot,
+                                                         uint32_t *__restrict__ hop, uint32_t *__restrict__ run_count) {
+  const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+  if (p >= G.m) return;
+  const uint32_t s = seg_of(G, p);
+  const uint64_t so = G.off[G.first + s] - G.base, len = G.off[G.first + s + 1] - G.off[G.first + s];
+  const uint64_t i = p - so, rem = len - i;
+  const uint8_t *a = reinterpret_cast<const uint8_t *>(G.src[G.first + s]) + i;
+  const uint32_t valid = rem < (uint64_t)K.key_bytes ? (uint32_t)rem : (uint32_t)K.key_bytes;
+  const uint64_t be = next_bytes(a, i, rem, valid);
+  const uint64_t bytes = be >> (64 - 8 * K.key_bytes);
+  const uint32_t e = G.m - 1 - rend[G.m - 1 - p];   // p <= e < so + len
+  const uint32_t L = e - p + 1;
+  uint32_t side = 0, mag = 0, hp = 0;
+  const bool run = L >= (uint32_t)K.key_bytes;
+  if (run) {
+    const uint32_t c = (uint32_t)(be >> 56);
+    if ((uint64_t)L < rem) side = a[L] > c ? 1u : 0u;   // a[L] is the byte behind the run, inside the segment
+    const uint32_t lc = L < cap ? L : cap;
+    mag = side ? cap - lc : lc;
+    hp = L < cap ? L : 0;
+  }
+  const int low = bwt::SIDE_BITS + K.run_bits;
+  key[p] = ((uint64_t)s << (8 * K.key_bytes + bwt::VALID_BITS + low)) | (bytes << (bwt::VALID_BITS + low)) |
+           ((uint64_t)valid << low) | ((uint64_t)side << K.run_bits) | mag;
+  val[p] = p;
+  uslot[p] = p;
+  hop[p] = hp;
+  const uint64_t runs = __ballot(run);   // lane 0 of a wavefront is live whenever one of its lanes is
+  if ((threadIdx.x & 63u) == 0 && runs) atomicAdd(run_count, (uint32_t)__popcll(runs));
+}
+
 // ------------------------------------------------------------------ a doubling round
 // key of an unresolved position i: (rank[i], rank[i + h] + 1), or 0 for the second half when i + h is past the end of
-// i's segment -- the shorter suffix sorts first
+// i's segment -- the shorter suffix sorts first.  RUNS: i + max(h, hop[i]) in the place of i + h.
+template <bool RUNS>
 __global__ __launch_bounds__(256) void k_round_keys(Sub G, uint32_t h, int lb, const uint32_t *__restrict__ rank,
                                                     const uint32_t *__restrict__ upos, uint32_t cnt,
-                                                    uint64_t *__restrict__ key) {
+                                                    uint64_t *__restrict__ key, const uint32_t *__restrict__ hop) {
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;
   if (t >= cnt) return;
   const uint32_t p = upos[t];
   const uint32_t s = seg_of(G, p);
   const uint64_t end = G.off[G.first + s + 1] - G.base;
+  if (RUNS) {
+    const uint32_t hp = hop[p];
+    if (hp > h) h = hp;
+  }
   const uint64_t q = (uint64_t)p + h;
   const uint64_t nx = q < end ? (uint64_t)rank[q] + 1 : 0;
   key[t] = ((uint64_t)rank[p] << lb) | nx;
@@ -226,11 +300,14 @@ struct spring_bwt_ctx {
   hipStream_t st = nullptr;
   uint64_t block_bytes = DEFAULT_BLOCK_BYTES;
   uint64_t workspace_bytes = 0;   // 0: from the free HBM
+  bool run_keys = false;
+  uint32_t cap_bits = 0;          // 0: the layout's own run_bits
   bool have = false;
   spring_bwt_info info;
   std::vector<uint64_t> off;      // num_segments + 1
   std::vector<int32_t> seg_stream;
   std::vector<uint32_t> seg_block, seg_cut;
+  std::vector<uint64_t> round_entries;   // per sort round: the entries sorted, summed over the sub-batches
   DBuf out, primary, nidx, indexes;
 };
 
@@ -246,6 +323,7 @@ void drop_result(spring_bwt_ctx *ctx) {
   ctx->seg_stream.clear();
   ctx->seg_block.clear();
   ctx->seg_cut.clear();
+  ctx->round_entries.clear();
   memset(&ctx->info, 0, sizeof(ctx->info));
 }
 
@@ -256,7 +334,7 @@ int ctx_begin(spring_bwt_ctx *ctx) {
 }
 
 struct Work {   // the arrays of a sub-batch, sized for the largest one
-  DBuf key, key2, posA, posB, uslot, uslot2, rank, sa, f, h, tmp, counter;
+  DBuf key, key2, posA, posB, uslot, uslot2, rank, sa, f, h, hop, tmp, counter;   // hop: with run keys only
   size_t tmp_bytes = 0;
 };
 
@@ -272,27 +350,45 @@ int tmp_need(hipStream_t st, uint64_t n, size_t *out) {
 }
 
 // One sub-batch: suffix order of its positions, then the output bytes and the index tables of its segments.
-int sort_sub(spring_bwt_ctx *ctx, const Sub &G, uint64_t longest, Work &W, uint64_t *rounds_out, double *ms) {
+int sort_sub(spring_bwt_ctx *ctx, const Sub &G, uint64_t longest, Work &W, uint64_t *rounds_out, uint64_t *runs_out,
+             double *ms) {
   hipStream_t st = ctx->st;
   const uint32_t m = G.m;
+  const bool runs = ctx->run_keys;
   *rounds_out = 0;
+  *runs_out = 0;
   Events ev;
   for (int k = 0; k < 6; k++) HIPCHK(hipEventCreate(&ev.e[k]));
   uint32_t *uslot = W.uslot.as<uint32_t>(), *uslot2 = W.uslot2.as<uint32_t>();
   if (m) {
     const bwt::KeyLayout K = bwt::key_layout(G.count);
+    const bwt::RunKeyLayout RK = bwt::run_key_layout(G.count);
+    const uint32_t cap = (1u << (ctx->cap_bits ? (int)ctx->cap_bits : RK.run_bits)) - 1;   // cap_bits <= run_bits: transform()
     const int lb = bwt::bits_for((uint64_t)m + 1);
     const int max_rounds = bwt::max_rounds(longest);
     uint32_t cnt = m;
-    uint64_t h = (uint64_t)K.key_bytes;
-    unsigned bits = (unsigned)K.total_bits;
+    uint64_t h = (uint64_t)(runs ? RK.key_bytes : K.key_bytes);
+    unsigned bits = (unsigned)(runs ? RK.total_bits : K.total_bits);
+    if (runs) HIPCHK(hipMemsetAsync(W.counter.as<uint32_t>() + 1, 0, 4, st));
     for (int round = 0; round < max_rounds && cnt > 0; round++) {
       HIPCHK(hipEventRecord(ev.e[0], st));
-      if (round == 0)
+      const uint32_t hh = (uint32_t)std::min<uint64_t>(h, 0x80000000ull);
+      if (round == 0 && runs) {   // the two scan words are free before the first sort
+        hipLaunchKernelGGL(k_run_ends, grid(m), dim3(256), 0, st, G, W.f.as<uint32_t>());
+        size_t sb = W.tmp_bytes;
+        HIPCHK(rocprim::inclusive_scan(W.tmp.p, sb, W.f.as<uint32_t>(), W.h.as<uint32_t>(), (size_t)m,
+                                       rocprim::maximum<uint32_t>(), st));
+        hipLaunchKernelGGL(k_first_keys_runs, grid(m), dim3(256), 0, st, G, RK, cap, W.h.as<uint32_t>(), W.key.as<uint64_t>(),
+                           W.posA.as<uint32_t>(), uslot, W.hop.as<uint32_t>(), W.counter.as<uint32_t>() + 1);
+      } else if (round == 0) {
         hipLaunchKernelGGL(k_first_keys, grid(m), dim3(256), 0, st, G, K, W.key.as<uint64_t>(), W.posA.as<uint32_t>(), uslot);
-      else
-        hipLaunchKernelGGL(k_round_keys, grid(cnt), dim3(256), 0, st, G, (uint32_t)std::min<uint64_t>(h, 0x80000000ull), lb,
-                           W.rank.as<uint32_t>(), W.posA.as<uint32_t>(), cnt, W.key.as<uint64_t>());
+      } else if (runs) {
+        hipLaunchKernelGGL(k_round_keys<true>, grid(cnt), dim3(256), 0, st, G, hh, lb, W.rank.as<uint32_t>(),
+                           W.posA.as<uint32_t>(), cnt, W.key.as<uint64_t>(), W.hop.as<uint32_t>());
+      } else {
+        hipLaunchKernelGGL(k_round_keys<false>, grid(cnt), dim3(256), 0, st, G, hh, lb, W.rank.as<uint32_t>(),
+                           W.posA.as<uint32_t>(), cnt, W.key.as<uint64_t>(), (const uint32_t *)nullptr);
+      }
       HIPCHK(hipEventRecord(ev.e[1], st));
       size_t tb = 0;
       HIPCHK(sr::sort_pairs(st, nullptr, tb, nullptr, nullptr, nullptr, nullptr, cnt, bits));
@@ -321,6 +417,8 @@ int sort_sub(spring_bwt_ctx *ctx, const Sub &G, uint64_t longest, Work &W, uint6
         ms[k] += x;
       }
       if (left > cnt) return fail(SPRING_REORDER_E_HIP, "the unresolved positions grew from %u to %u", cnt, left);
+      if (ctx->round_entries.size() <= (size_t)round) ctx->round_entries.resize((size_t)round + 1, 0);
+      ctx->round_entries[(size_t)round] += cnt;
       cnt = left;
       std::swap(uslot, uslot2);
       if (round > 0) h *= 2;
@@ -328,6 +426,11 @@ int sort_sub(spring_bwt_ctx *ctx, const Sub &G, uint64_t longest, Work &W, uint6
       (*rounds_out)++;
     }
     if (cnt) return fail(SPRING_REORDER_E_HIP, "%u suffixes unresolved after %d rounds", cnt, max_rounds);
+    if (runs) {
+      uint32_t n_runs = 0;
+      HIPCHK(rd(st, &n_runs, W.counter.as<uint32_t>() + 1, 4));
+      *runs_out = n_runs;
+    }
   }
   HIPCHK(hipEventRecord(ev.e[0], st));
   if (m) hipLaunchKernelGGL(k_gather, grid((uint64_t)m + 3 + 3, 1024), dim3(256), 0, st, G, W.sa.as<uint32_t>(),
@@ -373,14 +476,22 @@ int transform(spring_bwt_ctx *ctx, const std::vector<uint64_t> &src, spring_bwt_
   }
   I.workspace_bytes = budget;
   std::vector<uint64_t> first(S + 2);
-  const int64_t nsub = bwt::plan_sub_batches(off.data(), S, budget, first.data());
+  const bool runs = ctx->run_keys;
+  const int64_t nsub = bwt::plan_sub_batches(off.data(), S, budget, first.data(), runs);
   if (nsub < 0) {
     const uint64_t s = (uint64_t)(-1 - nsub);
     return fail(SPRING_REORDER_E_ARG, "segment %llu of %llu bytes needs %llu bytes of workspace, the budget is %llu",
                 (unsigned long long)s, (unsigned long long)(off[s + 1] - off[s]),
-                (unsigned long long)bwt::workspace_need(off[s + 1] - off[s], 1), (unsigned long long)budget);
+                (unsigned long long)bwt::workspace_need(off[s + 1] - off[s], 1, runs), (unsigned long long)budget);
   }
   I.sub_batches = (uint64_t)nsub;
+  if (runs && ctx->cap_bits)
+    for (int64_t b = 0; b < nsub; b++) {
+      const int own = bwt::run_key_layout(first[b + 1] - first[b]).run_bits;
+      if ((int)ctx->cap_bits > own)
+        return fail(SPRING_REORDER_E_ARG, "cap_bits %u, but the run-key layout of a sub-batch of %llu segments has %d bits",
+                    ctx->cap_bits, (unsigned long long)(first[b + 1] - first[b]), own);
+    }
   if (S == 0) {
     ctx->info = I;
     ctx->have = true;
@@ -409,6 +520,7 @@ int transform(spring_bwt_ctx *ctx, const std::vector<uint64_t> &src, spring_bwt_
     DALLOC(W.uslot, mmax * 4); DALLOC(W.uslot2, mmax * 4);
     DALLOC(W.rank, mmax * 4); DALLOC(W.sa, mmax * 4);
     DALLOC(W.f, mmax * 4); DALLOC(W.h, mmax * 4);
+    if (runs) DALLOC(W.hop, mmax * 4);
   }
   DALLOC(W.counter, 16);
   double ms[5] = {0, 0, 0, 0, 0};
@@ -420,10 +532,11 @@ int transform(spring_bwt_ctx *ctx, const std::vector<uint64_t> &src, spring_bwt_
     G.count = (uint32_t)(first[b + 1] - first[b]);
     G.base = off[first[b]];
     G.m = (uint32_t)(off[first[b + 1]] - off[first[b]]);
-    uint64_t longest = 0, rounds = 0;
+    uint64_t longest = 0, rounds = 0, run_positions = 0;
     for (uint64_t s = first[b]; s < first[b + 1]; s++) longest = std::max(longest, off[s + 1] - off[s]);
-    const int r = sort_sub(ctx, G, longest, W, &rounds, ms);
+    const int r = sort_sub(ctx, G, longest, W, &rounds, &run_positions, ms);
     if (r) return r;
+    I.run_positions += run_positions;
     I.rounds = std::max(I.rounds, rounds);
     I.rounds_total += rounds;
   }
@@ -476,6 +589,15 @@ int spring_bwt_set_workspace_bytes(spring_bwt_ctx *ctx, uint64_t workspace_bytes
 }
 
 uint64_t spring_bwt_workspace_need(uint64_t bytes, uint64_t segments) { return bwt::workspace_need(bytes, segments); }
+
+int spring_bwt_set_run_keys(spring_bwt_ctx *ctx, int32_t on, uint32_t cap_bits) {
+  if (!ctx) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  if (cap_bits == 1 || cap_bits > (uint32_t)bwt::MAX_RUN_BITS)
+    return fail(SPRING_REORDER_E_ARG, "cap_bits must be 0 or in 2 .. %d (got %u)", bwt::MAX_RUN_BITS, cap_bits);
+  ctx->run_keys = on != 0;
+  ctx->cap_bits = cap_bits;
+  return 0;
+}
 
 int spring_bwt_from_host(spring_bwt_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const uint64_t *seg_off,
                          uint64_t num_segments, spring_bwt_info *info) {
@@ -544,6 +666,43 @@ int spring_bwt_from_streams(spring_bwt_ctx *ctx, spring_streams_ctx *streams, ui
   return r;
 }
 
+int spring_bwt_from_qualid(spring_bwt_ctx *ctx, spring_qualid_ctx *q, int32_t kind, uint64_t block_bytes,
+                           spring_bwt_info *info) {
+  if (!ctx || !q) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  (void)hipSetDevice(ctx->dev);
+  drop_result(ctx);
+  if (kind != SPRING_QUALID_QUALITY && kind != SPRING_QUALID_ID)
+    return fail(SPRING_REORDER_E_ARG, "kind must be SPRING_QUALID_QUALITY or SPRING_QUALID_ID (got %d)", kind);
+  if (block_bytes > bwt::MAX_SEGMENT)
+    return fail(SPRING_REORDER_E_ARG, "block_bytes must be 0 or in 1 .. 2^30 (got %llu)", (unsigned long long)block_bytes);
+  sr::QualIdView V;
+  int r = sr::qualid_view(q, &V);
+  if (r) return r;
+  if (!V.have[kind]) return fail(SPRING_REORDER_E_STATE, "the quality / id context holds no %s blocks", kind ? "id" : "quality");
+  if (V.dev != ctx->dev) return fail(SPRING_REORDER_E_ARG, "quality / id and block-sort contexts live on different devices");
+  const uint64_t nb = V.info.num_blocks, B = block_bytes ? block_bytes : QUALID_BLOCK_BYTES;
+  const uint64_t *tab = V.table[kind];
+  std::vector<uint64_t> src;
+  ctx->off.assign(1, 0);
+  for (uint64_t b = 0; b < nb; b++) {
+    if (tab[b + 1] < tab[b] || tab[b + 1] > V.info.bytes[kind])
+      return fail(SPRING_REORDER_E_STATE, "the quality / id context's block table is damaged");
+    for (uint64_t lo = tab[b], c = 0; lo < tab[b + 1]; lo += B, c++) {
+      const uint64_t len = std::min(B, tab[b + 1] - lo);
+      src.push_back(reinterpret_cast<uint64_t>(V.bytes[kind] + lo));
+      ctx->off.push_back(ctx->off.back() + len);
+      ctx->seg_stream.push_back(kind == SPRING_QUALID_QUALITY ? SPRING_BWT_SRC_QUALITY : SPRING_BWT_SRC_ID);
+      ctx->seg_block.push_back((uint32_t)b);
+      ctx->seg_cut.push_back((uint32_t)c);
+    }
+  }
+  if ((r = ctx_begin(ctx))) { drop_result(ctx); return r; }
+  r = transform(ctx, src, info);
+  if (ctx->st) (void)hipStreamSynchronize(ctx->st);
+  if (r) drop_result(ctx);
+  return r;
+}
+
 int spring_bwt_get_info(spring_bwt_ctx *ctx, spring_bwt_info *info) {
   if (!ctx || !info) return fail(SPRING_REORDER_E_ARG, "NULL argument");
   if (!ctx->have) return fail(SPRING_REORDER_E_STATE, "nothing transformed yet");
@@ -572,6 +731,13 @@ int spring_bwt_segments(spring_bwt_ctx *ctx, int32_t *stream, uint32_t *block, u
   if (stream && S) memcpy(stream, ctx->seg_stream.data(), S * 4);
   if (block && S) memcpy(block, ctx->seg_block.data(), S * 4);
   if (cut && S) memcpy(cut, ctx->seg_cut.data(), S * 4);
+  return 0;
+}
+
+int spring_bwt_round_entries(spring_bwt_ctx *ctx, uint64_t *entries, uint64_t max_entries) {
+  if (!ctx) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  if (!ctx->have) return fail(SPRING_REORDER_E_STATE, "nothing transformed yet");
+  for (uint64_t k = 0; entries && k < max_entries; k++) entries[k] = k < ctx->round_entries.size() ? ctx->round_entries[k] : 0;
   return 0;
 }
 
