@@ -5,7 +5,8 @@
  * Replaces the quality / id side of spring::preprocess (reference src/preprocess.cpp:200-250, the quantize_quality
  * table lookup of util.cpp:143-149 included) and spring::reorder_compress_quality_id
  * (src/reorder_compress_quality_id.cpp:34-235) up to, not including, their codec calls (quantize_quality_qvz,
- * BSC_str_array_compress, compress_id_block):
+ * BSC_str_array_compress, compress_id_block).  compress_id_block is the id codec stage (spring_idcodec.h), which takes
+ * the id result of a context where it lies in HBM; the block sort of BSC_str_array_compress is spring_bwt.h:
  *
  *   order     read_order.bin as the encoder leaves it, BEFORE pe_encode (spring.cpp:176-206).  Single-end:
  *             order_array[order[i]] = i, U = num_reads units.  Paired-end: for i < num_reads, if order[i] <

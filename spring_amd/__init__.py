@@ -12,3 +12,4 @@ from .fastq_out import FastqOutStage  # noqa: F401,E402
 from .gzip import GzipStage  # noqa: F401,E402
 from .bwt import BwtStage  # noqa: F401,E402
 from .unbwt import UnbwtStage  # noqa: F401,E402
+from .idcodec import IdCodecStage  # noqa: F401,E402

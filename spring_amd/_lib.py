@@ -76,6 +76,13 @@ UNBWT_EXPORTS = [
 ]
 UNBWT_PASSES = 6  # SPRING_UNBWT_PASSES
 
+# include/spring_idcodec.h: a list of its own as well
+IDCODEC_EXPORTS = [
+    "spring_idcodec_create", "spring_idcodec_destroy", "spring_idcodec_set_workspace_bytes",
+    "spring_idcodec_workspace_need", "spring_idcodec_from_qualid", "spring_idcodec_from_host", "spring_idcodec_download",
+    "spring_idcodec_symbols", "spring_idcodec_get_info",
+]
+
 
 class Opts(C.Structure):
     _fields_ = [("device", C.c_int32), ("num_chains", C.c_uint32), ("num_thr", C.c_int32),
@@ -194,6 +201,14 @@ class UnbwtInfo(C.Structure):
             v = getattr(self, k)
             d[k] = list(v) if hasattr(v, "__len__") else v
         return d
+
+
+class IdCodecInfo(C.Structure):
+    _fields_ = ([(k, C.c_uint64) for k in ("num_lines", "num_blocks", "num_symbols", "bytes", "max_tokens", "sub_batches")]
+                + [("ms_tokens", C.c_double), ("ms_coder", C.c_double)])
+
+    def asdict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class DecodeInfo(C.Structure):
@@ -398,6 +413,20 @@ def lib():
     L.spring_unbwt_download.argtypes = [vp, u8p, vp]
     L.spring_unbwt_get_info.argtypes = [vp, C.POINTER(UnbwtInfo)]
     L.spring_unbwt_decode_inplace.argtypes = [vp, u8p, C.c_int32, C.c_int32, C.c_uint8, vp]
+    L.spring_idcodec_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.spring_idcodec_destroy.argtypes = [vp]
+    L.spring_idcodec_destroy.restype = None
+    L.spring_idcodec_set_workspace_bytes.argtypes = [vp, C.c_uint64]
+    L.spring_idcodec_workspace_need.argtypes = [C.c_uint64, C.c_uint64]
+    L.spring_idcodec_workspace_need.restype = C.c_uint64
+    L.spring_idcodec_from_qualid.argtypes = [vp, vp, C.POINTER(IdCodecInfo)]
+    L.spring_idcodec_from_host.argtypes = [vp, u8p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(IdCodecInfo)]
+    L.spring_idcodec_download.argtypes = [vp, u8p, vp]
+    L.spring_idcodec_symbols.argtypes = [vp, vp, vp]
+    L.spring_idcodec_get_info.argtypes = [vp, C.POINTER(IdCodecInfo)]
+    for name in IDCODEC_EXPORTS:
+        if name not in ("spring_idcodec_destroy", "spring_idcodec_workspace_need"):
+            getattr(L, name).restype = C.c_int
     for name in UNBWT_EXPORTS:
         if name not in ("spring_unbwt_destroy", "spring_unbwt_workspace_need"):
             getattr(L, name).restype = C.c_int

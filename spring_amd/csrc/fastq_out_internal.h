@@ -28,6 +28,7 @@ struct QualIdView {
   uint32_t num_reads_per_block;
   bool have[2];                   // a result of this kind exists
   const uint8_t *bytes[2];        // device: all blocks back to back (info.bytes[kind] bytes)
+  const uint32_t *len[2];         // device: num_units line lengths in slot order (without the id's '\n')
   const uint64_t *table[2];       // host: num_blocks + 1 block offsets
 };
 int qualid_view(spring_qualid_ctx *ctx, QualIdView *v);   // fails unless the context holds a result

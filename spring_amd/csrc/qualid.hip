@@ -739,6 +739,7 @@ int qualid_view(spring_qualid_ctx *ctx, QualIdView *v) {
   for (int k = 0; k < 2; k++) {
     v->have[k] = ctx->have_kind[k];
     v->bytes[k] = ctx->out[k].as<uint8_t>();
+    v->len[k] = ctx->len[k].as<uint32_t>();
     v->table[k] = ctx->table[k].data();
   }
   return 0;
