@@ -40,6 +40,42 @@ constexpr uint32_t ALT_KEY = 1u << 28;
 // DevParams::ord: bit 31 of a class-list entry = "this chain's proposal was lost" (local chain indices stay below 2^28 too)
 constexpr uint32_t ORD_LOST = 1u << 31;
 
+// Write-through stores: what a round or mark kernel leaves behind for the NEXT launch -- chain
+// records, count columns, emission records, proposal words, class lists -- is never read again inside the launch, and the
+// chain's next round runs on whatever CU (and XCD: the L2s are private) is free.  A plain store keeps the line dirty in
+// the L2 until the end-of-kernel release writes all of them back, which is on the group's critical path; these stores
+// send the bytes on as they are made and leave nothing to write back.  Global stores, never flat.  Two rules for every
+// site: all stores of a launch to one location use one flavour, and no wavefront loads, later in the same launch, bytes
+// stored this way (its L1 may still hold the old line).
+typedef uint32_t wt_u32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store_wt(uint4 *p, uint4 v) {
+  const wt_u32x4_t d = {v.x, v.y, v.z, v.w};
+  // (the nop: the compiler does not know that the store still reads d when the statement ends)
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(d) : "memory");
+}
+__device__ __forceinline__ void store_wt(int4 *p, int4 v) {
+  store_wt(reinterpret_cast<uint4 *>(p), make_uint4((uint32_t)v.x, (uint32_t)v.y, (uint32_t)v.z, (uint32_t)v.w));
+}
+__device__ __forceinline__ void store_wt(uint32_t *p, uint32_t v) {
+  __hip_atomic_store((__attribute__((address_space(1))) uint32_t *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void store_wt(uint64_t *p, uint64_t v) {
+  __hip_atomic_store((__attribute__((address_space(1))) uint64_t *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void store_wt(unsigned long long *p, unsigned long long v) {
+  store_wt(reinterpret_cast<uint64_t *>(p), (uint64_t)v);
+}
+__device__ __forceinline__ void store_wt(uint2 *p, uint2 v) {
+  store_wt(reinterpret_cast<uint64_t *>(p), ((uint64_t)v.y << 32) | v.x);
+}
+// 16 bytes as two 8-byte stores the compiler schedules itself: for the one-chain round kernels, whose variant at 64 VGPRs
+// spills a register to scratch memory around the asm statement above (64 bytes of header and one record per chain and round)
+__device__ __forceinline__ void store_wt_2x8(uint4 *p, uint4 v) {
+  uint64_t *q = reinterpret_cast<uint64_t *>(p);
+  store_wt(q, ((uint64_t)v.y << 32) | v.x);
+  store_wt(q + 1, ((uint64_t)v.w << 32) | v.z);
+}
+
 // Per-chain state (one greedy chain == one reference OpenMP thread, reorder.h:351-431).
 // The 64-byte header is wave-uniform: the chain kernels fetch it with ONE scalar load into 16 SGPRs (no VGPRs, no
 // LDS round trip per field), update it with scalar ALU and write it back as 16-byte quarters (lane q stores quarter

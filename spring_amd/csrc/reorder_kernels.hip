@@ -751,7 +751,7 @@ __device__ __forceinline__ void pack_consensus(WaveLds *ws, int R, int lane, Cha
     const uint32_t up = spread16(a >> 16) | (spread16(b >> 16) << 1);
     const uint64_t limb = ((uint64_t)up << 32) | lo;
     uint64_t *dst = isrev ? c->revref : c->ref;
-    dst[2 * myk + (hi ? 1 : 0)] = limb;
+    store_wt(&dst[2 * myk + (hi ? 1 : 0)], limb);
     if (lds_refs) lds_refs[(isrev ? LDS_LIMBS : 0) + LDS_PAD + 2 * myk + (hi ? 1 : 0)] = limb;
   }
 }
@@ -887,7 +887,7 @@ __device__ __forceinline__ int wave_update_compute(const DevParams &P, uint32_t 
     overflow = __any(mxl > 255);
     for (int p = lane; p < M; p += 64) {
       const int4 t = make_int4(wl->cnt[0][p], wl->cnt[1][p], wl->cnt[2][p], wl->cnt[3][p]);
-      if (out_wide) nxt[p] = t; else nxt8[p] = pack8(t);
+      if (out_wide) store_wt(nxt + p, t); else store_wt(nxt8 + p, pack8(t));
     }
     return Rl;
   }
@@ -912,7 +912,7 @@ __device__ __forceinline__ int wave_update_compute(const DevParams &P, uint32_t 
           add_hot(t, cidx_of_code(cur_base(ws->rd, p, n, rev)));
         }
       }
-      if (out_wide) nxt[p] = t; else nxt8[p] = pack8(t);
+      if (out_wide) store_wt(nxt + p, t); else store_wt(nxt8 + p, pack8(t));
       mx = max(max(mx, max(t.x, t.y)), max(t.z, t.w));
       if (p < Rn) ws->code[p] = (uint8_t)(reset ? code : argmax_code(t));  // reset: consensus = the read itself
     }
@@ -941,6 +941,10 @@ __device__ __forceinline__ void load_hot(const Chain *c, ChainHot &h) {
   h.alt1 = v[13];
   h.pad[0] = h.pad[1] = 0;
 }
+// SPLIT8: a quarter goes out as two 8-byte stores (store_wt_2x8: the one-chain kernels, which have no scratch at 64 VGPRs
+// that way) instead of one 16-byte store (k_round_mc).  Both forms are sc1 global stores -- one flavour: kernels that share
+// a chain's header between launches (k_init_chains, the round kernels, k_long_fin) may differ in the form.
+template <bool SPLIT8>
 __device__ __forceinline__ void store_hot(Chain *c, const ChainHot &h, int lane, int q_lo = 0, int q_hi = 4) {
   if (lane >= q_lo && lane < q_hi) {
     const uint32_t plo = (uint32_t)(unsigned long long)h.ref_pos, phi = (uint32_t)((unsigned long long)h.ref_pos >> 32);
@@ -949,7 +953,8 @@ __device__ __forceinline__ void store_hot(Chain *c, const ChainHot &h, int lane,
     q.y = lane == 0 ? phi : lane == 1 ? h.first_rid : lane == 2 ? h.num_reads_thr : h.alt1;
     q.z = lane == 0 ? (uint32_t)h.ref_len : lane == 1 ? h.n_emit : lane == 2 ? h.num_unmatched_past : 0u;
     q.w = lane == 0 ? h.e_slot : lane == 1 ? h.n_single : lane == 2 ? h.prop_rid : 0u;
-    reinterpret_cast<uint4 *>(&c->h)[lane] = q;
+    if (SPLIT8) store_wt_2x8(reinterpret_cast<uint4 *>(&c->h) + lane, q);
+    else store_wt(reinterpret_cast<uint4 *>(&c->h) + lane, q);
   }
 }
 __device__ __forceinline__ uint32_t uni_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
@@ -976,7 +981,7 @@ __global__ __launch_bounds__(256) void k_init_chains(DevParams P) {
   }
   if (!start) {
     h.done = 1;
-    store_hot(c, h, lane);
+    store_hot<true>(c, h, lane);
     if (lane == 0 && P.prop) P.prop[cid] = (unsigned long long)PK_DONE << 32;
     return;
   }
@@ -988,7 +993,7 @@ __global__ __launch_bounds__(256) void k_init_chains(DevParams P) {
   h.e_slot = li * CHUNK; h.s_slot = li * CHUNK;  // first chunk is pre-assigned; Globals.*_alloc start at K*CHUNK
   h.ref_len = Rn; h.cnt_buf = 1; h.cnt_wide = 0;
   if (P.fused) h.prop_kind = PROP_FRESH;
-  store_hot(c, h, lane);
+  store_hot<true>(c, h, lane);
   if (lane == 0) {
     c->n_unmatched = 1;
     if (P.prop) P.prop[cid] = (unsigned long long)PK_NONE << 32;
@@ -1713,7 +1718,7 @@ __device__ __forceinline__ int search_step(const DevParams &P, Chain *c, uint32_
       // the last-ranked needy chain proposes the lowest seed of the round: it alone moves the cursor
       h.cursor_writer = last;
       if (lane == 0) {
-        if (WORD) P.prop[cid] = ((unsigned long long)PK_SEED << 32) | seed | (last ? PK_CURSOR_BIT : 0ull);
+        if (WORD) store_wt(&P.prop[cid], ((unsigned long long)PK_SEED << 32) | seed | (last ? PK_CURSOR_BIT : 0ull));
         if (DIRECT) atomicMin(&P.resv[seed], cid);
       }
     } else {
@@ -1723,9 +1728,9 @@ __device__ __forceinline__ int search_step(const DevParams &P, Chain *c, uint32_
       // this round the whole pool is taken -- the cursor goes to -1 (find_seed relies on "every read above the
       // cursor is taken" AND on the cursor having passed every seed ever handed out)
       h.cursor_writer = last;
-      if (WORD && lane == 0) P.prop[cid] = ((unsigned long long)PK_NOSEED << 32) | (last ? PK_CURSOR_BIT : 0ull);
+      if (WORD && lane == 0) store_wt(&P.prop[cid], ((unsigned long long)PK_NOSEED << 32) | (last ? PK_CURSOR_BIT : 0ull));
     }
-    store_hot(c, h, lane, 2, 4);
+    store_hot<true>(c, h, lane, 2, 4);
     PTW(11);
     return -2;
   }
@@ -1741,9 +1746,9 @@ __device__ __forceinline__ int search_step(const DevParams &P, Chain *c, uint32_
   const bool new_iter = !h.retrying;
   if (h.stop_searching) {
     h.prop_kind = PROP_NONE;
-    store_hot(c, h, lane, 2, 4);
+    store_hot<true>(c, h, lane, 2, 4);
     if (lane == 0) {
-      if (WORD) P.prop[cid] = ((unsigned long long)PK_NONE << 32) | (h.left_search ? PK_WILLNEED_BIT : 0ull);
+      if (WORD) store_wt(&P.prop[cid], ((unsigned long long)PK_NONE << 32) | (h.left_search ? PK_WILLNEED_BIT : 0ull));
       if (STATS && new_iter) c->st_iter++;
     }
     return -3;
@@ -1816,7 +1821,7 @@ __device__ __forceinline__ int search_step(const DevParams &P, Chain *c, uint32_
   if (LONG && handed_over) {
     // the iteration bookkeeping above stays; the proposal fields still hold the last proposal (k_long derives the
     // resume point from them exactly as this search did) and k_long writes the new one
-    store_hot(c, h, lane, 2, 4);
+    store_hot<true>(c, h, lane, 2, 4);
     if (lane == 0) P.longq[2 + atomicAdd(&P.longq[0], 1u)] = cid - P.c0;
     return -4;
   }
@@ -1835,15 +1840,15 @@ __device__ __forceinline__ int search_step(const DevParams &P, Chain *c, uint32_
     } else {
       h.prop_kind = PROP_NONE;
     }
-    store_hot(c, h, lane, 2, 4);
+    store_hot<true>(c, h, lane, 2, 4);
   }
   if (lane == 0) {
     if (o.found) {
-      if (WORD) P.prop[cid] = ((unsigned long long)PK_MATCH << 32) | o.rid | ((unsigned long long)(TRIM ? h.alt1 : 0u) << PK_ALT_SHIFT);
+      if (WORD) store_wt(&P.prop[cid], ((unsigned long long)PK_MATCH << 32) | o.rid | ((unsigned long long)(TRIM ? h.alt1 : 0u) << PK_ALT_SHIFT));
       if (DIRECT) atomicMin(&P.resv[o.rid], cid);
     } else {
       // a failed left search sends the chain for a new seed (apply step): k_mg_mark puts it on the needy bitmap
-      if (WORD) P.prop[cid] = ((unsigned long long)PK_NONE << 32) | (left_search ? PK_WILLNEED_BIT : 0ull);
+      if (WORD) store_wt(&P.prop[cid], ((unsigned long long)PK_NONE << 32) | (left_search ? PK_WILLNEED_BIT : 0ull));
     }
     if (STATS) {
       c->st_probes += st_p; c->st_keyok += st_k; c->st_cands += st_c;
@@ -1904,7 +1909,7 @@ __device__ __forceinline__ uint32_t take_slot(uint32_t &slot, uint32_t *alloc, u
     uint32_t got = 0;
     if (lane == 0) got = atomicAdd(alloc, CHUNK);
     nx = uni_u32(got);
-    if (lane == 0) chunk[nx / CHUNK] = make_uint2(li, next_seq);  // the chunk's owner and the sequence number of its first record
+    if (lane == 0) store_wt(&chunk[nx / CHUNK], make_uint2(li, next_seq));  // the chunk's owner and the sequence number of its first record
   }
   slot = nx;
   return s0;
@@ -1918,8 +1923,8 @@ __device__ __forceinline__ void emit_rec(const DevParams &P, ChainHot &h, uint32
   const uint32_t idx = take_slot(slot, &P.glob->e_alloc, P.e_chunk, li, seq + 1, lane);
   h.e_slot = slot;
   if (lane == 0)
-    P.e_rec[idx] = make_uint4(rid, (uint32_t)(uint8_t)rc | ((uint32_t)(uint8_t)flag << 8), (uint32_t)pos,
-                              (uint32_t)((unsigned long long)pos >> 32));
+    store_wt_2x8(&P.e_rec[idx], make_uint4(rid, (uint32_t)(uint8_t)rc | ((uint32_t)(uint8_t)flag << 8), (uint32_t)pos,
+                                           (uint32_t)((unsigned long long)pos >> 32)));
 }
 __device__ __forceinline__ void emit_single(const DevParams &P, ChainHot &h, uint32_t li, uint32_t rid, int lane) {
   const uint32_t seq = h.n_single;
@@ -1927,7 +1932,7 @@ __device__ __forceinline__ void emit_single(const DevParams &P, ChainHot &h, uin
   uint32_t slot = h.s_slot;
   const uint32_t idx = take_slot(slot, &P.glob->s_alloc, P.s_chunk, li, seq + 1, lane);
   h.s_slot = slot;
-  if (lane == 0) P.s_rec[idx] = rid;
+  if (lane == 0) store_wt(&P.s_rec[idx], rid);
 }
 
 // One chain's phase B.  Resolves the proposal the chain made in the last search (lowest chain id holds resv[rid])
@@ -1949,7 +1954,7 @@ __device__ __forceinline__ bool apply_step(const DevParams &P, Chain *c, uint32_
       if (h.cursor_writer) *P.cursor = -1;  // (see search_step: the pool is exhausted)
     }
     h.cursor_writer = 0;
-    store_hot(c, h, lane);
+    store_hot<true>(c, h, lane);
     return false;
   }
   // who holds the read we proposed (load in flight while the update is computed)
@@ -1976,7 +1981,7 @@ __device__ __forceinline__ bool apply_step(const DevParams &P, Chain *c, uint32_
   static_assert(!OWNER_FIRST || DEFER, "OWNER_FIRST: fused rounds only (the cursor is k_mg_mark's)");
   if (OWNER_FIRST && kind != PROP_NONE && uni_u32(owner_v) != cid) {
     if (h.mode == MODE_SEARCH) h.retrying = 1;
-    store_hot(c, h, lane);
+    store_hot<true>(c, h, lane);
     if (lane == 0) atomicAdd((unsigned long long *)&c->st_lost, 1ull);
     return true;
   }
@@ -2000,7 +2005,7 @@ __device__ __forceinline__ bool apply_step(const DevParams &P, Chain *c, uint32_
   const uint32_t owner = uni_u32(owner_v);
   if (owner != cid) {  // lost the read: retry, nothing committed
     if (h.mode == MODE_SEARCH) h.retrying = 1;
-    store_hot(c, h, lane);
+    store_hot<true>(c, h, lane);
     if (lane == 0) atomicAdd((unsigned long long *)&c->st_lost, 1ull);  // no returned value: nothing to wait for
     return true;
   }
@@ -2055,7 +2060,7 @@ __device__ __forceinline__ bool apply_step(const DevParams &P, Chain *c, uint32_
       if (!DEFER && lane == 0) atomicOr(&P.needy[cid >> 5], 1u << (cid & 31));  // DEFER: k_mg_mark, from the PK_WILLNEED word
     }
   }
-  store_hot(c, h, lane);
+  store_hot<true>(c, h, lane);
   PT(5);
   return true;
 }
@@ -2119,7 +2124,7 @@ __device__ __forceinline__ void round_body(const DevParams &P) {
   if (lane < LDS_LIMBS) { s_refs[0][lane] = r0; s_refs[1][lane] = r1; }
   wave_sync();  // the update below rewrites s_refs
   if (h.done) {
-    if (lane == 0) P.prop[cid] = (unsigned long long)PK_DONE << 32;
+    if (lane == 0) store_wt(&P.prop[cid], (unsigned long long)PK_DONE << 32);
     return;
   }
   PTW(0);
@@ -2129,7 +2134,7 @@ __device__ __forceinline__ void round_body(const DevParams &P) {
   constexpr bool OWNER_FIRST = TRIM && !STATS;
 #endif
   if (!apply_step<NP, false, true, OWNER_FIRST>(P, c, cid, li, h, lane, &lds, nullptr, &s_refs[0][0])) {
-    if (lane == 0) P.prop[cid] = (unsigned long long)PK_DONE << 32;
+    if (lane == 0) store_wt(&P.prop[cid], (unsigned long long)PK_DONE << 32);
     PT_FLUSH(c);
     return;
   }
@@ -2751,13 +2756,13 @@ __global__ __launch_bounds__(256) void k_long_fin(DevParams P, int direct) {
   } else {
     h.prop_kind = PROP_NONE;
   }
-  store_hot(c, h, lane, 2, 4);
+  store_hot<true>(c, h, lane, 2, 4);
   if (lane == 0) {
     if (found) {
-      P.prop[cid] = ((unsigned long long)PK_MATCH << 32) | wrid | ((unsigned long long)h.alt1 << PK_ALT_SHIFT);
+      store_wt(&P.prop[cid], ((unsigned long long)PK_MATCH << 32) | wrid | ((unsigned long long)h.alt1 << PK_ALT_SHIFT));
       if (direct) atomicMin(&P.resv[wrid], cid);
     } else {
-      P.prop[cid] = ((unsigned long long)PK_NONE << 32) | (h.left_search ? PK_WILLNEED_BIT : 0ull);
+      store_wt(&P.prop[cid], ((unsigned long long)PK_NONE << 32) | (h.left_search ? PK_WILLNEED_BIT : 0ull));
     }
     c->st_long++;  // (the chain is this wavefront's alone)
   }
@@ -2834,8 +2839,8 @@ __global__ __launch_bounds__(256) void k_mg_mark(DevParams P) {
   const uint32_t na = (uint32_t)__popcll(__ballot(alive));
   const uint32_t w0 = (cid & ~63u) >> 5;  // a wavefront covers two bitmap words
   if (lane == 0 && (cid & ~63u) < P.Ktot) {
-    P.needy[w0] = (uint32_t)nb;
-    if ((cid & ~63u) + 32 < ((P.Ktot + 31) & ~31u)) P.needy[w0 + 1] = (uint32_t)(nb >> 32);
+    store_wt(&P.needy[w0], (uint32_t)nb);
+    if ((cid & ~63u) + 32 < ((P.Ktot + 31) & ~31u)) store_wt(&P.needy[w0 + 1], (uint32_t)(nb >> 32));
     if (nb) atomicAdd(&P.needy_cnt_next[cid >> 11], (uint32_t)__popcll(nb));
     P.alive_wave[cid >> 6] = na;  // summed by the host when it checks for the end (a same-address atomic per wavefront
                                   // was most of this kernel's time)
@@ -2860,11 +2865,11 @@ __global__ __launch_bounds__(256) void k_mg_mark(DevParams P) {
       uint32_t base = 0;
       for (int k = 0; k < cls; k++) base += s_wc[0][k] + s_wc[1][k] + s_wc[2][k] + s_wc[3][k];
       for (int w = 0; w < wv; w++) base += s_wc[w][cls];
-      P.ord[(size_t)blockIdx.x * MARK_BLOCK + base + mypos] = (cid - P.c0) | (lost ? ORD_LOST : 0u);  // (the verdict: apply_mc)
+      store_wt(&P.ord[(size_t)blockIdx.x * MARK_BLOCK + base + mypos], (cid - P.c0) | (lost ? ORD_LOST : 0u));  // (the verdict: apply_mc)
     }
     if (threadIdx.x == 0)
-      P.ord_cnt[blockIdx.x] = make_uint4(s_wc[0][0] + s_wc[1][0] + s_wc[2][0] + s_wc[3][0], s_wc[0][1] + s_wc[1][1] + s_wc[2][1] + s_wc[3][1],
-                                         s_wc[0][2] + s_wc[1][2] + s_wc[2][2] + s_wc[3][2], s_wc[0][3] + s_wc[1][3] + s_wc[2][3] + s_wc[3][3]);
+      store_wt(&P.ord_cnt[blockIdx.x], make_uint4(s_wc[0][0] + s_wc[1][0] + s_wc[2][0] + s_wc[3][0], s_wc[0][1] + s_wc[1][1] + s_wc[2][1] + s_wc[3][1],
+                                                  s_wc[0][2] + s_wc[1][2] + s_wc[2][2] + s_wc[3][2], s_wc[0][3] + s_wc[1][3] + s_wc[2][3] + s_wc[3][3]));
   }
 }
 // ---------------------------------------------- the two-group schedule (DevParams::phases = 2): one group's mark step
@@ -2942,14 +2947,14 @@ __global__ __launch_bounds__(64) void k_ph_mark(DevParams P) {
       } else if (pk == PK_NOSEED && (pv[j] & PK_CURSOR_BIT)) {
         *P.cursor = -1;
       }
-      P.won[cid - P.gg0] = wonv;
+      store_wt(&P.won[cid - P.gg0], wonv);
     }
     const uint64_t nb = __ballot(needy);
     const uint32_t na = (uint32_t)__popcll(__ballot(alive && inr[j]));
     const uint32_t cb = cbase + 64 * j;  // (g0 is a multiple of 2048: a sub-block covers two whole bitmap words of its group)
     if (lane == 0 && cb < gend) {
-      P.needy[cb >> 5] = (uint32_t)nb;
-      if (cb + 32 < ((gend + 31) & ~31u)) P.needy[(cb >> 5) + 1] = (uint32_t)(nb >> 32);
+      store_wt(&P.needy[cb >> 5], (uint32_t)nb);
+      if (cb + 32 < ((gend + 31) & ~31u)) store_wt(&P.needy[(cb >> 5) + 1], (uint32_t)(nb >> 32));
       if (nb) atomicAdd(&P.needy_cnt_next[cb >> 11], (uint32_t)__popcll(nb));
       P.alive_wave[cb >> 6] = na;
     }
@@ -2976,14 +2981,14 @@ __global__ __launch_bounds__(64) void k_ph_mark(DevParams P) {
       for (int j = 0; j < CPL; j++) {
         const uint64_t m = __ballot(cls[j] == k);
         if (cls[j] == k)
-          P.ord[(size_t)segi * MARK_BLOCK + run + (uint32_t)__popcll(m & ((1ull << lane) - 1))] =
-              (cbase + 64 * j + lane - P.c0) | (((lostm >> j) & 1u) ? ORD_LOST : 0u);
+          store_wt(&P.ord[(size_t)segi * MARK_BLOCK + run + (uint32_t)__popcll(m & ((1ull << lane) - 1))],
+                   (cbase + 64 * j + lane - P.c0) | (((lostm >> j) & 1u) ? ORD_LOST : 0u));
         run += (uint32_t)__popcll(m);
       }
       tot[k] = run - base;
       base = run;
     }
-    if (lane == 0) P.ord_cnt[segi] = make_uint4(tot[0], tot[1], tot[2], tot[3]);
+    if (lane == 0) store_wt(&P.ord_cnt[segi], make_uint4(tot[0], tot[1], tot[2], tot[3]));
   }
 }
 // The same step with four wavefronts per block of MARK_BLOCK chains and one chain per thread (k_mg_mark's shape): a quarter of
@@ -3040,7 +3045,7 @@ __global__ __launch_bounds__(256) void k_ph_mark_wide(DevParams P) {
     } else if (pk == PK_NOSEED && (pv & PK_CURSOR_BIT)) {
       *P.cursor = -1;
     }
-    P.won[t] = wonv;
+    store_wt(&P.won[t], wonv);
   }
   for (uint32_t j = t; j < P.gKg_other; j += gridDim.x * blockDim.x) {  // the other group's last winners: into this group's view
     const uint32_t w = j == t ? wo : P.won_other[j];
@@ -3056,8 +3061,8 @@ __global__ __launch_bounds__(256) void k_ph_mark_wide(DevParams P) {
   const uint32_t na = (uint32_t)__popcll(__ballot(alive));
   const uint32_t cb = cid & ~63u;  // (g0 is a multiple of 2048: a wavefront covers two whole bitmap words of its group)
   if (lane == 0 && cb < gend) {
-    P.needy[cb >> 5] = (uint32_t)nb;
-    if (cb + 32 < ((gend + 31) & ~31u)) P.needy[(cb >> 5) + 1] = (uint32_t)(nb >> 32);
+    store_wt(&P.needy[cb >> 5], (uint32_t)nb);
+    if (cb + 32 < ((gend + 31) & ~31u)) store_wt(&P.needy[(cb >> 5) + 1], (uint32_t)(nb >> 32));
     if (nb) atomicAdd(&P.needy_cnt_next[cid >> 11], (uint32_t)__popcll(nb));
     P.alive_wave[cid >> 6] = na;
   }
@@ -3078,11 +3083,11 @@ __global__ __launch_bounds__(256) void k_ph_mark_wide(DevParams P) {
       uint32_t base = 0;
       for (int k = 0; k < cls; k++) base += s_wc[0][k] + s_wc[1][k] + s_wc[2][k] + s_wc[3][k];
       for (int w = 0; w < wv; w++) base += s_wc[w][cls];
-      P.ord[(size_t)segi * MARK_BLOCK + base + mypos] = (cid - P.c0) | (lost ? ORD_LOST : 0u);
+      store_wt(&P.ord[(size_t)segi * MARK_BLOCK + base + mypos], (cid - P.c0) | (lost ? ORD_LOST : 0u));
     }
     if (threadIdx.x == 0)
-      P.ord_cnt[segi] = make_uint4(s_wc[0][0] + s_wc[1][0] + s_wc[2][0] + s_wc[3][0], s_wc[0][1] + s_wc[1][1] + s_wc[2][1] + s_wc[3][1],
-                                   s_wc[0][2] + s_wc[1][2] + s_wc[2][2] + s_wc[3][2], s_wc[0][3] + s_wc[1][3] + s_wc[2][3] + s_wc[3][3]);
+      store_wt(&P.ord_cnt[segi], make_uint4(s_wc[0][0] + s_wc[1][0] + s_wc[2][0] + s_wc[3][0], s_wc[0][1] + s_wc[1][1] + s_wc[2][1] + s_wc[3][1],
+                                            s_wc[0][2] + s_wc[1][2] + s_wc[2][2] + s_wc[3][2], s_wc[0][3] + s_wc[1][3] + s_wc[2][3] + s_wc[3][3]));
   }
 }
 // pass 1 of the alternatives schedule for one group (k_alt_resolve; before the group's k_ph_mark, behind the other group's last

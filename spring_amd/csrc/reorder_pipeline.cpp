@@ -1995,15 +1995,19 @@ static int run_chains_phased(spring_reorder_ctx *ctx, int R, bool timed) {
   hipStream_t sg[2] = {ctx->st, ctx->st2}, sc = ctx->st3;
   struct Group { uint64_t *taken; uint64_t round_no; } gp[2] = {{P.taken, 0}, {ctx->taken2, 0}};
   auto params_of = [&](int g) { return group_params(ctx, g, gp[g].round_no); };
-  hipEvent_t ev[2] = {nullptr, nullptr}, bev[2] = {nullptr, nullptr}, ev0 = nullptr, evt = nullptr;
+  // ev[], ev0, evt only order device work between streams: no system-scope fence (ORDER_ONLY).  What the host reads --
+  // alive_wave, copied out once a batch -- waits on cev[], recorded behind the batch's last mark steps with the fence.
+  constexpr unsigned ORDER_ONLY = hipEventDisableTiming | hipEventDisableSystemFence;
+  hipEvent_t ev[2] = {nullptr, nullptr}, cev[2] = {nullptr, nullptr}, bev[2] = {nullptr, nullptr}, ev0 = nullptr, evt = nullptr;
   struct EvFree { hipEvent_t *e; int n; ~EvFree() { for (int i = 0; i < n; i++) if (e[i]) (void)hipEventDestroy(e[i]); } };
-  EvFree g1{ev, 2}, g2{bev, 2}, g3{&ev0, 1}, g4{&evt, 1};
+  EvFree g1{ev, 2}, g2{bev, 2}, g3{&ev0, 1}, g4{&evt, 1}, g5{cev, 2};
   for (int i = 0; i < 2; i++) {
-    HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&ev[i], ORDER_ONLY));
+    HIPCHK(hipEventCreateWithFlags(&cev[i], hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&bev[i], hipEventDisableTiming));
   }
-  HIPCHK(hipEventCreateWithFlags(&ev0, hipEventDisableTiming));
-  HIPCHK(hipEventCreateWithFlags(&evt, hipEventDisableTiming));
+  HIPCHK(hipEventCreateWithFlags(&ev0, ORDER_ONLY));
+  HIPCHK(hipEventCreateWithFlags(&evt, ORDER_ONLY));
   std::vector<hipEvent_t> tev;  // opts.time_search: an event pair around every round-kernel launch, on the launch's stream
   struct TevFree { std::vector<hipEvent_t> &v; ~TevFree() { for (auto &e : v) (void)hipEventDestroy(e); } } tev_guard{tev};
   if (timed) {
@@ -2041,6 +2045,7 @@ static int run_chains_phased(spring_reorder_ctx *ctx, int R, bool timed) {
       }
       have_b = true;
     }
+    for (int g = 0; g < 2; g++) HIPCHK(hipEventRecord(cev[g], sg[g]));
     rounds += R;
     if (P.deep_bins && (ctx->dict[0].ndeep || ctx->dict[1].ndeep)) {
       // compaction of the deep bins (k_trim_bins moves bin entries: no search may run beside it): both groups meet here, every
@@ -2054,8 +2059,8 @@ static int run_chains_phased(spring_reorder_ctx *ctx, int R, bool timed) {
     return 0;
   };
   auto count_batch = [&](int slot) -> int {  // behind both groups' last mark steps of the batch
-    HIPCHK(hipStreamWaitEvent(sc, ev[0], 0));
-    HIPCHK(hipStreamWaitEvent(sc, ev[1], 0));
+    HIPCHK(hipStreamWaitEvent(sc, cev[0], 0));
+    HIPCHK(hipStreamWaitEvent(sc, cev[1], 0));
     HIPCHK(hipMemcpyAsync(h_aw + (size_t)slot * nw, P.alive_wave, nw * 4, hipMemcpyDeviceToHost, sc));
     HIPCHK(hipEventRecord(bev[slot], sc));
     return 0;

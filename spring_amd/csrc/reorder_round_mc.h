@@ -157,7 +157,7 @@ __device__ __forceinline__ int update_mc(const DevParams &P, uint32_t li, GLds<N
         }
         if (p < Rn) codes |= cdx << (2 * e);
       }
-      if (p0 < hiP) *reinterpret_cast<uint4 *>(nxt8 + p0) = make_uint4(t4[0], t4[1], t4[2], t4[3]);
+      if (p0 < hiP) store_wt(reinterpret_cast<uint4 *>(nxt8 + p0), make_uint4(t4[0], t4[1], t4[2], t4[3]));
     } else {
 #define MC_LOAD_CNT(I) (cur_wide ? cur[(I)] : unpack8(cur8[(I)]))
       for (int e = 0; e < 4; e++) {
@@ -179,7 +179,7 @@ __device__ __forceinline__ int update_mc(const DevParams &P, uint32_t li, GLds<N
             add_hot(t, cidx_of_code(cur_base(rd + 1, p, n, rev)));
           }
         }
-        if (out_wide) nxt[p] = t; else nxt8[p] = pack8(t);
+        if (out_wide) store_wt(nxt + p, t); else store_wt(nxt8 + p, pack8(t));
         ovf = ovf || max(max(t.x, t.y), max(t.z, t.w)) > 255;
         if (p < Rn) codes |= (uint32_t)(reset ? code : argmax_code(t)) << (2 * e);
       }
@@ -207,7 +207,7 @@ __device__ __forceinline__ void commit_consensus(const DevParams &P, GLds<NQ, KA
   const bool in = gl < P.W;
   const uint64_t limb = in ? S.nref[gl] : 0ull;
   if (gl < GLds<NQ, KA>::WMAX) S.refs[0][LDS_PAD + gl] = limb;
-  if (in) c->ref[gl] = limb;
+  if (in) store_wt(&c->ref[gl], limb);
   wave_sync();
   if (gl < GLds<NQ, KA>::WMAX) S.refs[1][LDS_PAD + gl] = revref_limb(S.refs[0] + LDS_PAD, R, gl);
   wave_sync();
@@ -263,7 +263,7 @@ __device__ __forceinline__ void commit_consensus_ka(const DevParams &P, GLds<NQ,
   if (mode == 0) kf &= ~ka_stale(df, gshfl_down1_u64(df));
   wave_sync();
   if (gl < WM) { S.refs[0][LDS_PAD + gl] = limb; S.ka[0][LDS_PAD + gl] = kf; }
-  if (in) c->ref[gl] = limb;
+  if (in) store_wt(&c->ref[gl], limb);
   wave_sync();
   const uint64_t rl = gl < WM ? revref_limb(S.refs[0] + LDS_PAD, R, gl) : 0ull;
   if (mode == 0) {
@@ -290,7 +290,7 @@ __device__ __forceinline__ uint32_t take_slot_mc(uint32_t &slot, uint32_t *alloc
     uint32_t got = 0;
     if (gl == 0) {
       got = atomicAdd(alloc, CHUNK);
-      chunk[got / CHUNK] = make_uint2(li, next_seq);
+      store_wt(&chunk[got / CHUNK], make_uint2(li, next_seq));
     }
     nx = (uint32_t)__shfl((int)got, 0, G);
   }
@@ -305,8 +305,8 @@ __device__ __forceinline__ void emit_rec_mc(const DevParams &P, ChainHot &h, uin
   const uint32_t idx = take_slot_mc(slot, &P.glob->e_alloc, P.e_chunk, li, seq + 1, gl);
   h.e_slot = slot;
   if (gl == 0)
-    P.e_rec[idx] = make_uint4(rid, (uint32_t)(uint8_t)rc | ((uint32_t)(uint8_t)flag << 8), (uint32_t)pos,
-                              (uint32_t)((unsigned long long)pos >> 32));
+    store_wt(&P.e_rec[idx], make_uint4(rid, (uint32_t)(uint8_t)rc | ((uint32_t)(uint8_t)flag << 8), (uint32_t)pos,
+                                       (uint32_t)((unsigned long long)pos >> 32)));
 }
 __device__ __forceinline__ void emit_single_mc(const DevParams &P, ChainHot &h, uint32_t li, uint32_t rid, int gl) {
   const uint32_t seq = h.n_single;
@@ -314,7 +314,7 @@ __device__ __forceinline__ void emit_single_mc(const DevParams &P, ChainHot &h, 
   uint32_t slot = h.s_slot;
   const uint32_t idx = take_slot_mc(slot, &P.glob->s_alloc, P.s_chunk, li, seq + 1, gl);
   h.s_slot = slot;
-  if (gl == 0) P.s_rec[idx] = rid;
+  if (gl == 0) store_wt(&P.s_rec[idx], rid);
 }
 
 // phase B of one chain (apply_step with the shared state deferred to k_mg_mark).  false: the chain is done.
@@ -329,12 +329,12 @@ __device__ __forceinline__ bool apply_mc(const DevParams &P, Chain *c, uint32_t 
   if (h.finishing) {  // seed-needing chain found the pool empty
     if (h.prev_unmatched) emit_single_mc(P, h, li, h.prev, gl);
     h.done = 1; h.finishing = 0;
-    store_hot(c, h, gl);
+    store_hot<false>(c, h, gl);
     return false;
   }
   if (lost) {  // (a match or a seed) lost the read: retry, nothing committed
     if (h.mode == MODE_SEARCH) h.retrying = 1;
-    store_hot(c, h, gl, 3, 4);
+    store_hot<false>(c, h, gl, 3, 4);
     if (gl == 0) atomicAdd((unsigned long long *)&c->st_lost, 1ull);
     return true;
   }
@@ -400,7 +400,7 @@ __device__ __forceinline__ bool apply_mc(const DevParams &P, Chain *c, uint32_t 
     if (!h.left_search) { h.left_search = 1; h.ref_pos = 0; }
     else { h.left_search = 0; h.mode = MODE_NEED_SEED; }  // (k_mg_mark put the chain on the needy bitmap: PK_WILLNEED)
   }
-  store_hot(c, h, gl);
+  store_hot<false>(c, h, gl);
   return true;
 }
 
@@ -1119,16 +1119,16 @@ __device__ __forceinline__ void search_mc(const DevParams &P, Chain *c, uint32_t
       h.prop_rid = (uint32_t)seed;
       h.cursor_writer = is_last;  // the last-ranked needy chain proposes the lowest seed of the round
       if (gl == 0) {
-        P.prop[cid] = ((unsigned long long)PK_SEED << 32) | (uint32_t)seed | (is_last ? PK_CURSOR_BIT : 0ull);
+        store_wt(&P.prop[cid], ((unsigned long long)PK_SEED << 32) | (uint32_t)seed | (is_last ? PK_CURSOR_BIT : 0ull));
         atomicMin(&P.resv[seed], cid);  // (multi-GPU pools too: the rank's own proposals are settled here, k_mg_resolve adds the other ranks')
       }
     } else {
       h.prop_kind = PROP_NONE;
       h.finishing = 1;  // no reads left (reorder.h:593-599); applied in phase B
       // (the last-ranked chain finding nothing means the pool is exhausted: k_mg_mark sends the cursor to -1)
-      if (gl == 0) P.prop[cid] = ((unsigned long long)PK_NOSEED << 32) | (is_last ? PK_CURSOR_BIT : 0ull);
+      if (gl == 0) store_wt(&P.prop[cid], ((unsigned long long)PK_NOSEED << 32) | (is_last ? PK_CURSOR_BIT : 0ull));
     }
-    store_hot(c, h, gl, 2, 4);
+    store_hot<false>(c, h, gl, 2, 4);
     PT(23);
     return;
   }
@@ -1141,8 +1141,8 @@ __device__ __forceinline__ void search_mc(const DevParams &P, Chain *c, uint32_t
   }
   if (h.stop_searching) {
     h.prop_kind = PROP_NONE;
-    store_hot(c, h, gl, 2, 4);
-    if (gl == 0) P.prop[cid] = ((unsigned long long)PK_NONE << 32) | (h.left_search ? PK_WILLNEED_BIT : 0ull);
+    store_hot<false>(c, h, gl, 2, 4);
+    if (gl == 0) store_wt(&P.prop[cid], ((unsigned long long)PK_NONE << 32) | (h.left_search ? PK_WILLNEED_BIT : 0ull));
     return;
   }
   const int ref_len = h.ref_len;
@@ -1171,15 +1171,15 @@ __device__ __forceinline__ void search_mc(const DevParams &P, Chain *c, uint32_t
     h.prop_rev = (uint32_t)(((wcode >> 1) & 1) | ((wcode & 1) << 1));  // rev | dict << 1
     h.prop_kind = PROP_MATCH;
     if (gl == 0) {
-      P.prop[cid] = ((unsigned long long)PK_MATCH << 32) | wrid;
+      store_wt(&P.prop[cid], ((unsigned long long)PK_MATCH << 32) | wrid);
       atomicMin(&P.resv[wrid], cid);
     }
   } else {
     h.prop_kind = PROP_NONE;
     // a failed left search sends the chain for a new seed (apply step): k_mg_mark puts it on the needy bitmap
-    if (gl == 0) P.prop[cid] = ((unsigned long long)PK_NONE << 32) | (h.left_search ? PK_WILLNEED_BIT : 0ull);
+    if (gl == 0) store_wt(&P.prop[cid], ((unsigned long long)PK_NONE << 32) | (h.left_search ? PK_WILLNEED_BIT : 0ull));
   }
-  store_hot(c, h, gl, 2, 4);
+  store_hot<false>(c, h, gl, 2, 4);
 }
 
 }  // namespace mc
@@ -1262,7 +1262,7 @@ __device__ __forceinline__ void round_mc_body(const DevParams &P) {
   }
   wave_sync();
   if (h.done) {
-    if (gl == 0) P.prop[cid] = (unsigned long long)PK_DONE << 32;
+    if (gl == 0) store_wt(&P.prop[cid], (unsigned long long)PK_DONE << 32);
     return;
   }
   if (!seeker) {  // revref = the reverse complement of ref[0, ref_len): rebuilt, not kept in the chain record (commit_consensus)
@@ -1271,14 +1271,14 @@ __device__ __forceinline__ void round_mc_body(const DevParams &P) {
   }
   PTW(16);
   if (!mc::apply_mc<NQ, KA>(P, c, li, h, S, gl, lost)) {
-    if (gl == 0) P.prop[cid] = (unsigned long long)PK_DONE << 32;
+    if (gl == 0) store_wt(&P.prop[cid], (unsigned long long)PK_DONE << 32);
     return;
   }
   PT(17);
   mc::search_mc<NQ, MG, KA>(P, c, cid, h, S, (lds_u32_t *)s_stage, lane, gl);
   if constexpr (KA) if (!seeker && h.mode == MODE_SEARCH) {  // what the chain knows now, for its next round
     wave_sync();
-    if (gl < 8) c->revref[8 + gl] = S.ka[gl >> 2][GL::PAD + (gl < 4 ? P.ka_lo : 0) + (gl & 3)];
+    if (gl < 8) store_wt(&c->revref[8 + gl], S.ka[gl >> 2][GL::PAD + (gl < 4 ? P.ka_lo : 0) + (gl & 3)]);
   }
   PTW(24);
 #ifdef SR_PHASE_TIMING  // (experiment builds) the wavefront's table goes to the chain of its first lane still here
