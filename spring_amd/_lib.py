@@ -98,48 +98,38 @@ class Opts(C.Structure):
                 ("sort_prefix_bits", C.c_int32), ("dict_build_mode", C.c_int32), ("strand_filter", C.c_int32)]
 
 
+class Info(C.Structure):
+    """What the library reports about a finished call; asdict() gives array fields as lists."""
+
+    def asdict(self):
+        d = {}
+        for k, _ in self._fields_:
+            v = getattr(self, k)
+            d[k] = list(v) if hasattr(v, "__len__") else v
+        return d
+
+
 class FastqInfo(C.Structure):
     _fields_ = [("num_reads", C.c_uint32 * 2), ("num_reads_clean", C.c_uint32 * 2), ("num_reads_N", C.c_uint32 * 2),
                 ("max_readlen", C.c_uint32), ("pad", C.c_uint32), ("ms_device", C.c_double)]
 
 
-class EncoderInfo(C.Structure):
+class EncoderInfo(Info):
     _fields_ = ([(k, C.c_uint64) for k in ("n_aligned", "n_total", "seq_len", "noise_bytes", "n_noisepos",
                                            "unaligned_bytes", "len_unaligned", "num_contigs")]
                 + [(k, C.c_uint32) for k in ("matched_s", "matched_N", "align_passes", "max_bin")]
                 + [("ms_device", C.c_double), ("ms_phase", C.c_double * 8)])
 
-    def asdict(self):
-        d = {}
-        for k, _ in self._fields_:
-            v = getattr(self, k)
-            d[k] = list(v) if hasattr(v, "__len__") else v
-        return d
 
-
-class StreamsInfo(C.Structure):
+class StreamsInfo(Info):
     _fields_ = ([("num_units", C.c_uint64), ("num_blocks", C.c_uint64), ("bytes", C.c_uint64 * STREAMS_NUM),
                  ("flag_count", C.c_uint64 * 5), ("pos_escapes", C.c_uint64), ("n_aligned", C.c_uint64),
                  ("ms_device", C.c_double), ("ms_file", C.c_double)])
 
-    def asdict(self):
-        d = {}
-        for k, _ in self._fields_:
-            v = getattr(self, k)
-            d[k] = list(v) if hasattr(v, "__len__") else v
-        return d
 
-
-class QualIdInfo(C.Structure):
+class QualIdInfo(Info):
     _fields_ = [("num_units", C.c_uint64), ("num_blocks", C.c_uint64), ("bytes", C.c_uint64 * 2),
                 ("bytes_changed", C.c_uint64), ("max_len", C.c_uint32 * 2), ("ms_device", C.c_double)]
-
-    def asdict(self):
-        d = {}
-        for k, _ in self._fields_:
-            v = getattr(self, k)
-            d[k] = list(v) if hasattr(v, "__len__") else v
-        return d
 
 
 class FastqOutParams(C.Structure):
@@ -155,77 +145,43 @@ class FastqOutSources(C.Structure):
                 ("id_ctx", C.c_void_p), ("ids", C.c_void_p), ("id_bytes", C.c_uint64), ("id_block_off", C.c_void_p)]
 
 
-class FastqOutInfo(C.Structure):
+class FastqOutInfo(Info):
     _fields_ = [("num_units", C.c_uint64), ("first_slot", C.c_uint64), ("bytes", C.c_uint64),
                 ("ms_device", C.c_double), ("ms_file", C.c_double)]
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class GzipInfo(C.Structure):
+class GzipInfo(Info):
     _fields_ = ([(k, C.c_uint64) for k in ("num_members", "bytes_in", "bytes_out", "chunk_bytes", "num_chunks",
                                            "chunks_stored")]
                 + [("ms_device", C.c_double), ("ms_file", C.c_double), ("ms_pass", C.c_double * 6),
                    ("num_batches", C.c_uint64)])
 
-    def asdict(self):
-        d = {}
-        for k, _ in self._fields_:
-            v = getattr(self, k)
-            d[k] = list(v) if hasattr(v, "__len__") else v
-        return d
 
-
-class BwtInfo(C.Structure):
+class BwtInfo(Info):
     _fields_ = ([(k, C.c_uint64) for k in ("num_segments", "bytes", "max_segment", "sub_batches", "rounds",
                                            "rounds_total", "workspace_bytes")]
                 + [("ms_device", C.c_double), ("ms_pass", C.c_double * 5), ("run_positions", C.c_uint64)])
 
-    def asdict(self):
-        d = {}
-        for k, _ in self._fields_:
-            v = getattr(self, k)
-            d[k] = list(v) if hasattr(v, "__len__") else v
-        return d
 
-
-class UnbwtInfo(C.Structure):
+class UnbwtInfo(Info):
     _fields_ = ([(k, C.c_uint64) for k in ("num_segments", "bytes", "max_segment", "sub_batches", "heads", "head_spacing",
                                            "max_walk", "rank_rounds", "workspace_bytes")]
                 + [("ms_device", C.c_double), ("ms_pass", C.c_double * UNBWT_PASSES)])
 
-    def asdict(self):
-        d = {}
-        for k, _ in self._fields_:
-            v = getattr(self, k)
-            d[k] = list(v) if hasattr(v, "__len__") else v
-        return d
 
-
-class IdCodecInfo(C.Structure):
+class IdCodecInfo(Info):
     _fields_ = ([(k, C.c_uint64) for k in ("num_lines", "num_blocks", "num_symbols", "bytes", "max_tokens", "sub_batches")]
                 + [("ms_tokens", C.c_double), ("ms_coder", C.c_double)])
 
-    def asdict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class DecodeInfo(C.Structure):
+class DecodeInfo(Info):
     _fields_ = ([(k, C.c_uint64) for k in ("seq_len", "first_block", "num_blocks", "num_units")]
                 + [("bases", C.c_uint64 * 2)]
                 + [(k, C.c_uint64) for k in ("n_aligned", "n_unaligned", "pos_escapes")]
                 + [("ms_device", C.c_double), ("ms_file", C.c_double)])
 
-    def asdict(self):
-        d = {}
-        for k, _ in self._fields_:
-            v = getattr(self, k)
-            d[k] = list(v) if hasattr(v, "__len__") else v
-        return d
 
-
-class Stats(C.Structure):
+class Stats(Info):
     _fields_ = ([(k, C.c_uint64) for k in ("n_reads", "n_matched", "n_single", "unmatched", "probes", "keyok",
                                           "cands", "hits", "iterations", "rounds", "lost")]
                 + [("numkeys", C.c_uint64 * 2), ("dict_numreads", C.c_uint64 * 2)]
@@ -241,13 +197,14 @@ class Stats(C.Structure):
                    ("strand_filter", C.c_uint64), ("strand_filter_dropped", C.c_uint64),
                    ("strand_filter_build", C.c_uint64)])
 
-    def asdict(self):
-        d = {}
-        for k, _ in self._fields_:
-            v = getattr(self, k)
-            d[k] = list(v) if hasattr(v, "__len__") else v
-        return d
 
+# every export returns int (0 or a negative error code) except these
+NOT_INT = {"spring_reorder_last_error": C.c_char_p, "spring_synth_dna_bytes": C.c_size_t,
+           "spring_reorder_default_opts": None, "spring_reorder_trim_pool": None, "spring_mg_comm_destroy": None}
+NOT_INT.update({p + "_destroy": None for p in ("spring_reorder", "spring_encoder", "spring_streams", "spring_decode",
+                                               "spring_qualid", "spring_fastq_out", "spring_gzip", "spring_bwt",
+                                               "spring_unbwt", "spring_idcodec")})
+NOT_INT.update({p + "_workspace_need": C.c_uint64 for p in ("spring_bwt", "spring_unbwt", "spring_idcodec")})
 
 # spring_mg_allgather_fn (include/spring_reorder.h): host_buf, slice_off, slice_bytes, total_bytes, user -> 0 on success
 MG_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p)
@@ -267,13 +224,10 @@ def lib():
     L = C.CDLL(LIB_PATH)
     vp, u8p = C.c_void_p, C.c_void_p
     L.spring_reorder_default_opts.argtypes = [C.POINTER(Opts)]
-    L.spring_reorder_last_error.restype = C.c_char_p
-    L.spring_reorder_trim_pool.restype = None
     L.spring_reorder_run.argtypes = [C.c_char_p, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32,
                                      C.POINTER(Opts)]
     L.spring_reorder_create.argtypes = [C.POINTER(vp), C.POINTER(Opts)]
     L.spring_reorder_destroy.argtypes = [vp]
-    L.spring_reorder_destroy.restype = None
     L.spring_reorder_load_dna.argtypes = [vp, u8p, C.c_size_t, C.c_uint32, C.c_uint32]
     L.spring_reorder_load_dna_device.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int32]
     L.spring_reorder_build_dict.argtypes = [vp]
@@ -293,7 +247,6 @@ def lib():
     L.spring_mg_comm_create_rccl.argtypes = [C.POINTER(vp), C.c_int32, vp, C.c_uint32, C.c_uint32]
     L.spring_mg_comm_create_host.argtypes = [C.POINTER(vp), MG_ALLGATHER_FN, vp, C.c_uint32, C.c_uint32]
     L.spring_mg_comm_destroy.argtypes = [vp]
-    L.spring_mg_comm_destroy.restype = None
     L.spring_reorder_mg_run.argtypes = [vp, vp, C.c_uint32]
     L.spring_reorder_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.spring_reorder_download.argtypes = [vp] + [vp] * 8
@@ -310,7 +263,6 @@ def lib():
                                        C.POINTER(C.c_double)]
     L.spring_order_pe_encode.argtypes = [vp, C.c_uint32, vp, C.POINTER(C.c_double)]
     L.spring_order_correct.argtypes = [vp, C.c_uint64, vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
-    L.spring_synth_dna_bytes.restype = C.c_size_t
     L.spring_synth_dna_bytes.argtypes = [C.c_uint32, C.c_uint32]
     L.spring_synth_dna_host.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32]
     L.spring_synth_genome_host.argtypes = [u8p, C.c_uint64, C.c_uint64, C.c_uint32]
@@ -319,7 +271,6 @@ def lib():
     L.spring_reorder_download_dna.argtypes = [vp, u8p, C.c_size_t]
     L.spring_encoder_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_encoder_destroy.argtypes = [vp]
-    L.spring_encoder_destroy.restype = None
     L.spring_encoder_encode_reorder.argtypes = [vp, vp, u8p, C.c_uint64, vp, C.c_uint32, C.POINTER(EncoderInfo)]
     L.spring_encoder_download.argtypes = [vp] + [vp] * 9
     L.spring_encoder_download_seq_packed.argtypes = [vp, vp, vp]
@@ -333,7 +284,6 @@ def lib():
                                             C.c_uint32, C.POINTER(Opts), C.POINTER(EncoderInfo)]
     L.spring_streams_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_streams_destroy.argtypes = [vp]
-    L.spring_streams_destroy.restype = None
     L.spring_streams_from_encoder.argtypes = [vp, vp, C.c_uint32, C.c_int32, C.c_int32, C.c_uint32, C.c_int32,
                                               C.POINTER(StreamsInfo)]
     L.spring_streams_from_host.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp,
@@ -344,7 +294,6 @@ def lib():
                                      C.POINTER(StreamsInfo)]
     L.spring_decode_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_decode_destroy.argtypes = [vp]
-    L.spring_decode_destroy.restype = None
     L.spring_decode_seq_from_encoder.argtypes = [vp, vp]
     L.spring_decode_seq_from_host.argtypes = [vp, C.c_int32, vp, vp, vp]
     L.spring_decode_seq_from_files.argtypes = [vp, C.c_char_p, C.c_int32]
@@ -357,7 +306,6 @@ def lib():
     L.spring_decode_get_info.argtypes = [vp, C.POINTER(DecodeInfo)]
     L.spring_qualid_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_qualid_destroy.argtypes = [vp]
-    L.spring_qualid_destroy.restype = None
     L.spring_qualid_order_from_host.argtypes = [vp, vp, C.c_uint32, C.c_int32]
     L.spring_qualid_order_from_encoder.argtypes = [vp, vp, C.c_uint32, C.c_int32]
     L.spring_qualid_from_fastq.argtypes = [vp, u8p, C.c_size_t, C.c_int32, u8p, C.c_uint32, C.POINTER(QualIdInfo)]
@@ -369,7 +317,6 @@ def lib():
                                     C.POINTER(C.c_double)]
     L.spring_fastq_out_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_fastq_out_destroy.argtypes = [vp]
-    L.spring_fastq_out_destroy.restype = None
     L.spring_fastq_out_assemble.argtypes = [vp, C.POINTER(FastqOutParams), C.POINTER(FastqOutSources),
                                             C.POINTER(FastqOutInfo)]
     L.spring_fastq_out_download.argtypes = [vp, u8p, vp]
@@ -377,7 +324,6 @@ def lib():
     L.spring_fastq_out_get_info.argtypes = [vp, C.POINTER(FastqOutInfo)]
     L.spring_gzip_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_gzip_destroy.argtypes = [vp]
-    L.spring_gzip_destroy.restype = None
     L.spring_gzip_set_chunk_bytes.argtypes = [vp, C.c_uint32]
     L.spring_gzip_set_token_bytes.argtypes = [vp, C.c_uint64]
     L.spring_gzip_from_fastq_out.argtypes = [vp, vp, C.c_uint64, C.c_int32, C.POINTER(GzipInfo)]
@@ -387,11 +333,9 @@ def lib():
     L.spring_gzip_get_info.argtypes = [vp, C.POINTER(GzipInfo)]
     L.spring_bwt_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_bwt_destroy.argtypes = [vp]
-    L.spring_bwt_destroy.restype = None
     L.spring_bwt_set_block_bytes.argtypes = [vp, C.c_uint64]
     L.spring_bwt_set_workspace_bytes.argtypes = [vp, C.c_uint64]
     L.spring_bwt_workspace_need.argtypes = [C.c_uint64, C.c_uint64]
-    L.spring_bwt_workspace_need.restype = C.c_uint64
     L.spring_bwt_from_host.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint64, C.POINTER(BwtInfo)]
     L.spring_bwt_from_streams.argtypes = [vp, vp, C.c_uint32, C.POINTER(BwtInfo)]
     L.spring_bwt_download.argtypes = [vp, u8p, vp, vp, vp, vp]
@@ -403,10 +347,8 @@ def lib():
     L.spring_bwt_from_qualid.argtypes = [vp, vp, C.c_int32, C.c_uint64, C.POINTER(BwtInfo)]
     L.spring_unbwt_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_unbwt_destroy.argtypes = [vp]
-    L.spring_unbwt_destroy.restype = None
     L.spring_unbwt_set_workspace_bytes.argtypes = [vp, C.c_uint64]
     L.spring_unbwt_workspace_need.argtypes = [C.c_uint64, C.c_uint64]
-    L.spring_unbwt_workspace_need.restype = C.c_uint64
     L.spring_unbwt_set_head_spacing.argtypes = [vp, C.c_uint32]
     L.spring_unbwt_from_host.argtypes = [vp, u8p, C.c_uint64, vp, vp, C.c_uint64, C.POINTER(UnbwtInfo)]
     L.spring_unbwt_from_bwt.argtypes = [vp, vp, C.POINTER(UnbwtInfo)]
@@ -415,43 +357,15 @@ def lib():
     L.spring_unbwt_decode_inplace.argtypes = [vp, u8p, C.c_int32, C.c_int32, C.c_uint8, vp]
     L.spring_idcodec_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_idcodec_destroy.argtypes = [vp]
-    L.spring_idcodec_destroy.restype = None
     L.spring_idcodec_set_workspace_bytes.argtypes = [vp, C.c_uint64]
     L.spring_idcodec_workspace_need.argtypes = [C.c_uint64, C.c_uint64]
-    L.spring_idcodec_workspace_need.restype = C.c_uint64
     L.spring_idcodec_from_qualid.argtypes = [vp, vp, C.POINTER(IdCodecInfo)]
     L.spring_idcodec_from_host.argtypes = [vp, u8p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(IdCodecInfo)]
     L.spring_idcodec_download.argtypes = [vp, u8p, vp]
     L.spring_idcodec_symbols.argtypes = [vp, vp, vp]
     L.spring_idcodec_get_info.argtypes = [vp, C.POINTER(IdCodecInfo)]
-    for name in IDCODEC_EXPORTS:
-        if name not in ("spring_idcodec_destroy", "spring_idcodec_workspace_need"):
-            getattr(L, name).restype = C.c_int
-    for name in UNBWT_EXPORTS:
-        if name not in ("spring_unbwt_destroy", "spring_unbwt_workspace_need"):
-            getattr(L, name).restype = C.c_int
-    for name in BWT_EXPORTS:
-        if name not in ("spring_bwt_destroy", "spring_bwt_workspace_need"):
-            getattr(L, name).restype = C.c_int
-    for name in GZIP_EXPORTS:
-        if name != "spring_gzip_destroy":
-            getattr(L, name).restype = C.c_int
-    for name in FASTQ_OUT_EXPORTS:
-        if name != "spring_fastq_out_destroy":
-            getattr(L, name).restype = C.c_int
-    for name in QUALID_EXPORTS:
-        if name != "spring_qualid_destroy":
-            getattr(L, name).restype = C.c_int
-    for name in DECODE_EXPORTS:
-        if name != "spring_decode_destroy":
-            getattr(L, name).restype = C.c_int
-    for name in STREAMS_EXPORTS:
-        if name != "spring_streams_destroy":
-            getattr(L, name).restype = C.c_int
-    for name in EXPORTS:
-        if name not in ("spring_reorder_last_error", "spring_reorder_destroy", "spring_synth_dna_bytes",
-                        "spring_reorder_default_opts", "spring_reorder_trim_pool", "spring_encoder_destroy",
-                        "spring_mg_comm_destroy"):
-            getattr(L, name).restype = C.c_int
+    for name in (EXPORTS + STREAMS_EXPORTS + DECODE_EXPORTS + QUALID_EXPORTS + FASTQ_OUT_EXPORTS + GZIP_EXPORTS
+                 + BWT_EXPORTS + UNBWT_EXPORTS + IDCODEC_EXPORTS):
+        getattr(L, name).restype = NOT_INT.get(name, C.c_int)
     _lib = L
     return L

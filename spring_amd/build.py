@@ -13,7 +13,7 @@ SOURCES = ["reorder_kernels.hip", "reorder_pipeline.cpp", "reorder_files.cpp", "
            "gzip.hip", "bwt.hip", "unbwt.hip", "idcodec.hip"]
 HEADERS = ["reorder_device.h", "reorder_internal.h", "reorder_round_mc.h", "synth_common.h", "call_reorder.h",
            "encoder_internal.h", "streams_internal.h", "fastq_out_internal.h", "dict_build.h", "strand_filter.h",
-           "gzip_codes.h", "bwt_plan.h", "bwt_internal.h", "unbwt_plan.h"]
+           "gzip_codes.h", "bwt_plan.h", "bwt_internal.h", "unbwt_plan.h", "stage_host.h"]
 PUBLIC_HEADERS = ["spring_reorder.h", "spring_encoder.h", "spring_streams.h", "spring_decode.h", "spring_qualid.h",
                   "spring_fastq_out.h", "spring_gzip.h", "spring_bwt.h", "spring_unbwt.h", "spring_idcodec.h"]
 

@@ -27,40 +27,16 @@
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_bwt.h"
+#include "stage_host.h"
 #include "streams_internal.h"
 
-using sr::fail;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+using namespace sr;
 
 namespace {
 
 constexpr uint64_t DEFAULT_BLOCK_BYTES = 25ull * 1024 * 1024;   // bsc.cpp:80
 constexpr uint64_t QUALID_BLOCK_BYTES = 64ull * 1024 * 1024;    // "-b64", what BSC_str_array_compress passes
 constexpr uint64_t SORT_FIXED_BYTES = 8ull << 20;               // the sort's tables that do not grow with the input
-
-struct DBuf {
-  int dev = 0;
-  void *p = nullptr;
-  DBuf() = default;
-  DBuf(const DBuf &) = delete;
-  DBuf &operator=(const DBuf &) = delete;
-  ~DBuf() { release(); }
-  void release() { if (p) { sr::dev_free(dev, p); p = nullptr; } }
-  hipError_t alloc(int d, size_t bytes) { release(); dev = d; return sr::dev_alloc(d, bytes, &p); }
-  template <class T> T *as() const { return (T *)p; }
-};
-#define DALLOC(buf, bytes) HIPCHK((buf).alloc(dev, (bytes) ? (bytes) : 16))
-
-inline dim3 grid(uint64_t n, uint32_t per_block = 256) {
-  const uint64_t b = (n + per_block - 1) / per_block;
-  return dim3((unsigned)(b ? b : 1));
-}
 
 // A sub-batch: segments [first, first + count) of the batch; position p of it is byte off[first] + p of the batch.
 struct Sub {
@@ -283,16 +259,6 @@ __global__ __launch_bounds__(256) void k_indexes(Sub G, const uint32_t *__restri
   }
 }
 
-hipError_t rd(hipStream_t st, void *dst, const void *src, size_t n) {
-  hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st);
-  return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
-struct Events {
-  hipEvent_t e[8] = {};
-  ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 }  // namespace
 
 struct spring_bwt_ctx {
@@ -325,12 +291,6 @@ void drop_result(spring_bwt_ctx *ctx) {
   ctx->seg_cut.clear();
   ctx->round_entries.clear();
   memset(&ctx->info, 0, sizeof(ctx->info));
-}
-
-int ctx_begin(spring_bwt_ctx *ctx) {
-  HIPCHK(hipSetDevice(ctx->dev));
-  if (!ctx->st) HIPCHK(hipStreamCreate(&ctx->st));
-  return 0;
 }
 
 struct Work {   // the arrays of a sub-batch, sized for the largest one
@@ -503,10 +463,7 @@ int transform(spring_bwt_ctx *ctx, const std::vector<uint64_t> &src, spring_bwt_
   uint64_t mmax = 0;
   for (int64_t b = 0; b < nsub; b++) mmax = std::max(mmax, off[first[b + 1]] - off[first[b]]);
   Work W;
-  struct SyncOnExit {   // declared behind the buffers: whatever is in flight ends before they go back to the pool
-    hipStream_t st;
-    ~SyncOnExit() { (void)hipStreamSynchronize(st); }
-  } sync_on_exit{st};
+  SyncOnExit sync_on_exit{st};
   if (mmax) {
     size_t tb = 0;
     const int r = tmp_need(st, mmax, &tb);
@@ -553,11 +510,8 @@ extern "C" {
 
 int spring_bwt_create(int device, spring_bwt_ctx **out) {
   if (!out) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(SPRING_REORDER_E_HIP, "no HIP device available (the block-sort stage has no CPU fallback)");
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-  if (device >= ndev) return fail(SPRING_REORDER_E_ARG, "device %d out of range", device);
+  const int r = stage_device(&device, "the block-sort stage");
+  if (r) return r;
   spring_bwt_ctx *c = new spring_bwt_ctx();
   c->dev = device;
   memset(&c->info, 0, sizeof(c->info));
@@ -612,7 +566,7 @@ int spring_bwt_from_host(spring_bwt_ctx *ctx, const uint8_t *bytes, uint64_t nby
     return fail(SPRING_REORDER_E_ARG, "the segment offsets do not start at 0 and end at the %llu bytes", (unsigned long long)nbytes);
   for (uint64_t s = 0; s < num_segments; s++)
     if (seg_off[s + 1] < seg_off[s]) return fail(SPRING_REORDER_E_ARG, "the segment offsets decrease");
-  int r = ctx_begin(ctx);
+  int r = stream_begin(ctx->dev, &ctx->st);
   if (r) return r;
   const int dev = ctx->dev;
   DBuf up;
@@ -659,7 +613,7 @@ int spring_bwt_from_streams(spring_bwt_ctx *ctx, spring_streams_ctx *streams, ui
       }
     }
   }
-  if ((r = ctx_begin(ctx))) { drop_result(ctx); return r; }
+  if ((r = stream_begin(ctx->dev, &ctx->st))) { drop_result(ctx); return r; }
   r = transform(ctx, src, info);
   if (ctx->st) (void)hipStreamSynchronize(ctx->st);
   if (r) drop_result(ctx);
@@ -696,7 +650,7 @@ int spring_bwt_from_qualid(spring_bwt_ctx *ctx, spring_qualid_ctx *q, int32_t ki
       ctx->seg_cut.push_back((uint32_t)c);
     }
   }
-  if ((r = ctx_begin(ctx))) { drop_result(ctx); return r; }
+  if ((r = stream_begin(ctx->dev, &ctx->st))) { drop_result(ctx); return r; }
   r = transform(ctx, src, info);
   if (ctx->st) (void)hipStreamSynchronize(ctx->st);
   if (r) drop_result(ctx);

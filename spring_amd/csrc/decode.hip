@@ -27,16 +27,10 @@
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_decode.h"
+#include "stage_host.h"
 #include "streams_internal.h"
 
-using sr::fail;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+using namespace sr;
 
 namespace {
 
@@ -56,24 +50,6 @@ const char *const ERR_TEXT[] = {"a flag outside the alphabet of read_flag.txt",
 
 // per-unit counts scanned as u32 (totals <= 2 per unit, num_reads < 2^32)
 enum { C_REV, C_PP, C_RP, C_LINE, NC };
-
-struct DBuf {
-  int dev = 0;
-  void *p = nullptr;
-  DBuf() = default;
-  DBuf(const DBuf &) = delete;
-  DBuf &operator=(const DBuf &) = delete;
-  ~DBuf() { release(); }
-  void release() { if (p) { sr::dev_free(dev, p); p = nullptr; } }
-  hipError_t alloc(int d, size_t bytes) { release(); dev = d; return sr::dev_alloc(d, bytes, &p); }
-  template <class T> T *as() const { return (T *)p; }
-};
-#define DALLOC(buf, bytes) HIPCHK((buf).alloc(dev, (bytes) ? (bytes) : 16))
-
-inline dim3 grid(uint64_t n, uint32_t per_block = 256) {
-  const uint64_t b = (n + per_block - 1) / per_block;
-  return dim3((unsigned)(b ? b : 1));
-}
 
 struct In {   // device images of the window's streams (SPRING_STREAMS_* ids)
   const uint8_t *p[SPRING_STREAMS_NUM];
@@ -415,11 +391,6 @@ __global__ void k_unpack_seq(const uint8_t *__restrict__ packed, uint64_t nbytes
   for (int k = 0; k < 4; k++) out[4 * i + k] = (uint8_t)(w >> (8 * k));
 }
 
-hipError_t rd(hipStream_t st, void *dst, const void *src, size_t n) {
-  hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st);
-  return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
 }  // namespace
 
 struct spring_decode_ctx {
@@ -435,12 +406,6 @@ struct spring_decode_ctx {
 };
 
 namespace {
-
-int ctx_begin(spring_decode_ctx *ctx) {
-  HIPCHK(hipSetDevice(ctx->dev));
-  if (!ctx->st) HIPCHK(hipStreamCreate(&ctx->st));
-  return 0;
-}
 
 // the window's geometry and the host-side table checks; -> 0 or E_ARG
 int window(uint32_t first_block, uint32_t num_blocks, uint32_t N, bool pe, uint32_t B, uint64_t *nu) {
@@ -613,11 +578,8 @@ extern "C" {
 
 int spring_decode_create(int device, spring_decode_ctx **out) {
   if (!out) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(SPRING_REORDER_E_HIP, "no HIP device available (the decoder has no CPU fallback)");
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-  if (device >= ndev) return fail(SPRING_REORDER_E_ARG, "device %d out of range", device);
+  const int r = stage_device(&device, "the decoder");
+  if (r) return r;
   spring_decode_ctx *c = new spring_decode_ctx();
   c->dev = device;
   memset(&c->info, 0, sizeof(c->info));
@@ -642,7 +604,7 @@ int spring_decode_seq_from_encoder(spring_decode_ctx *ctx, spring_encoder_ctx *e
   int r = sr::encoder_view(enc, &V);
   if (r) return r;
   if (V.dev != ctx->dev) return fail(SPRING_REORDER_E_ARG, "encoder and decode contexts live on different devices");
-  if ((r = ctx_begin(ctx))) return r;
+  if ((r = stream_begin(ctx->dev, &ctx->st))) return r;
   ctx->have_seq = false;
   ctx->have = false;
   const int dev = ctx->dev;
@@ -671,7 +633,7 @@ int spring_decode_seq_from_host(spring_decode_ctx *ctx, int32_t num_thr_e, const
     }
   }
   if (np && !packed) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int r = ctx_begin(ctx);
+  int r = stream_begin(ctx->dev, &ctx->st);
   if (r) return r;
   ctx->have_seq = false;
   ctx->have = false;
@@ -708,7 +670,7 @@ int spring_decode_from_streams(spring_decode_ctx *ctx, spring_streams_ctx *s, sp
   int r = sr::streams_view(s, &V);
   if (r) return r;
   if (V.dev != ctx->dev) return fail(SPRING_REORDER_E_ARG, "streams and decode contexts live on different devices");
-  if ((r = ctx_begin(ctx))) return r;
+  if ((r = stream_begin(ctx->dev, &ctx->st))) return r;
   const uint64_t nb1 = V.info.num_blocks + 1;
   const uint64_t *tab[SPRING_STREAMS_NUM];
   for (int k = 0; k < SPRING_STREAMS_NUM; k++) tab[k] = V.table + k * nb1;
@@ -729,7 +691,7 @@ int spring_decode_from_host(spring_decode_ctx *ctx, const uint8_t *const *bytes,
     n[s] = block_off[s][num_blocks];
     if (n[s] && !bytes[s]) return fail(SPRING_REORDER_E_ARG, "NULL stream %d", s);
   }
-  int r = ctx_begin(ctx);
+  int r = stream_begin(ctx->dev, &ctx->st);
   if (r) return r;
   if (!ctx->have_seq) {
     ctx->have = false;

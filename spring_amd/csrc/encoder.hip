@@ -33,15 +33,9 @@
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_encoder.h"
+#include "stage_host.h"
 
-using sr::fail;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+using namespace sr;
 
 namespace {
 
@@ -754,25 +748,11 @@ __global__ void k_seq_pack(const uint8_t *__restrict__ refc, uint64_t base0, uin
   out[b] = (uint8_t)v;
 }
 
-inline dim3 grid(uint64_t n) { return dim3((unsigned)((n + 255) / 256 ? (n + 255) / 256 : 1)); }
 inline int bits_for(uint64_t v) {  // bits needed to hold values 0..v
   int b = 1;
   while (b < 64 && (v >> b)) b++;
   return b;
 }
-
-// device buffer from the library's pool
-struct DBuf {
-  int dev = 0;
-  void *p = nullptr;
-  DBuf() = default;
-  DBuf(const DBuf &) = delete;
-  DBuf &operator=(const DBuf &) = delete;
-  ~DBuf() { release(); }
-  void release() { if (p) { sr::dev_free(dev, p); p = nullptr; } }
-  hipError_t alloc(int d, size_t bytes) { release(); dev = d; return sr::dev_alloc(d, bytes, &p); }
-  template <class T> T *as() const { return (T *)p; }
-};
 
 }  // namespace
 
@@ -789,17 +769,12 @@ struct spring_encoder_ctx {
   std::vector<uint64_t> tid_seq;  // T + 1 offsets into refc
 };
 
-#define DALLOC(buf, bytes) HIPCHK((buf).alloc(dev, (bytes)))
-
 extern "C" {
 
 int spring_encoder_create(int device, spring_encoder_ctx **out) {
   if (!out) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(SPRING_REORDER_E_HIP, "no HIP device available (the encoder stage has no CPU fallback)");
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;  // like spring_reorder_create
-  if (device >= ndev) return fail(SPRING_REORDER_E_ARG, "device %d out of range", device);
+  const int r = stage_device(&device, "the encoder stage");
+  if (r) return r;
   spring_encoder_ctx *c = new spring_encoder_ctx();
   c->dev = device;
   memset(&c->info, 0, sizeof(c->info));

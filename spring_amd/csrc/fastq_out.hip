@@ -28,15 +28,9 @@
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_fastq_out.h"
+#include "stage_host.h"
 
-using sr::fail;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+using namespace sr;
 
 namespace {
 
@@ -56,24 +50,6 @@ constexpr int COPY_BLOCK_BYTES = 4096;   // 256 lanes x 16 bytes
 constexpr int LDS_RECS = 1024;           // record offsets of a copy block held in LDS (more: searched in memory)
 constexpr uint32_t NO_PATCH = 0xffffffffu;
 constexpr int NUMBERED_MAX = 13;         // '@' + 10 digits + '/' + mate
-
-struct DBuf {
-  int dev = 0;
-  void *p = nullptr;
-  DBuf() = default;
-  DBuf(const DBuf &) = delete;
-  DBuf &operator=(const DBuf &) = delete;
-  ~DBuf() { release(); }
-  void release() { if (p) { sr::dev_free(dev, p); p = nullptr; } }
-  hipError_t alloc(int d, size_t bytes) { release(); dev = d; return sr::dev_alloc(d, bytes, &p); }
-  template <class T> T *as() const { return (T *)p; }
-};
-#define DALLOC(buf, bytes) HIPCHK((buf).alloc(dev, (bytes) ? (bytes) : 16))
-
-inline dim3 grid(uint64_t n, uint32_t per_block = 256) {
-  const uint64_t b = (n + per_block - 1) / per_block;
-  return dim3((unsigned)(b ? b : 1));
-}
 
 // A source of bytes on the device: t is 16-byte aligned, the window's bytes are t[lo, lo + n), and t[0, limit) exists.
 struct Src {
@@ -285,15 +261,6 @@ __global__ __launch_bounds__(256) void k_assemble(CopyArg A) {
 }
 
 // ------------------------------------------------------------------ host side
-hipError_t rd(hipStream_t st, void *dst, const void *src, size_t n) {
-  hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st);
-  return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
-struct Events {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
 
 // the window's geometry (as the decoder's); -> 0 or E_ARG
 int window(uint32_t first_block, uint32_t num_blocks, uint32_t N, bool pe, uint32_t B, uint64_t *U_out, uint64_t *nu) {
@@ -335,12 +302,6 @@ void drop_result(spring_fastq_out_ctx *ctx) {
   ctx->text.release();
   ctx->rec_off.release();
   memset(&ctx->info, 0, sizeof(ctx->info));
-}
-
-int ctx_begin(spring_fastq_out_ctx *ctx) {
-  HIPCHK(hipSetDevice(ctx->dev));
-  if (!ctx->st) HIPCHK(hipStreamCreate(&ctx->st));
-  return 0;
 }
 
 // n host bytes into a device buffer at the host pointer's own offset inside a 16-byte word, so that the copy meets the
@@ -445,15 +406,12 @@ int assemble(spring_fastq_out_ctx *ctx, const spring_fastq_out_params &P, const 
     if (S.id_block_off && (r = check_table(S.id_block_off, nb, S.id_bytes, "id"))) return r;
   }
   // ---- the sources on the device
-  if ((r = ctx_begin(ctx))) return r;
+  if ((r = stream_begin(ctx->dev, &ctx->st))) return r;
   hipStream_t st = ctx->st;
   Events ev;
   HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b));
   DBuf up_bases, up_roff, up_qual, up_ids, d_qtab, d_itab, numbered_ids, le_buf, d_err, idstart, idlen, patch, recsz, tmp, bs;
-  struct SyncOnExit {   // declared behind the buffers: whatever is in flight ends before they go back to the pool
-    hipStream_t st;
-    ~SyncOnExit() { (void)hipStreamSynchronize(st); }
-  } sync_on_exit{st};
+  SyncOnExit sync_on_exit{st};
   Src bases, qual, ids;
   const uint64_t *roff = nullptr;
   const uint64_t *h_qtab = nullptr, *h_itab = nullptr;   // host tables of the window (nb + 1), or none
@@ -603,11 +561,8 @@ extern "C" {
 
 int spring_fastq_out_create(int device, spring_fastq_out_ctx **out) {
   if (!out) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(SPRING_REORDER_E_HIP, "no HIP device available (the FASTQ assembler has no CPU fallback)");
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-  if (device >= ndev) return fail(SPRING_REORDER_E_ARG, "device %d out of range", device);
+  const int r = stage_device(&device, "the FASTQ assembler");
+  if (r) return r;
   spring_fastq_out_ctx *c = new spring_fastq_out_ctx();
   c->dev = device;
   memset(&c->info, 0, sizeof(c->info));

@@ -13,15 +13,9 @@
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_reorder.h"
+#include "stage_host.h"
 
-using sr::fail;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+using namespace sr;
 
 namespace {
 
@@ -62,14 +56,6 @@ __global__ __launch_bounds__(256) void k_copy_records(const uint8_t *__restrict_
   if (lane == 0 && line_end[4 * i + 3] >= nbytes) dst[b - a] = '\n';
 }
 
-struct DBuf {
-  int dev = 0;
-  void *p = nullptr;
-  ~DBuf() { if (p) sr::dev_free(dev, p); }
-  hipError_t alloc(int d, size_t bytes) { dev = d; return sr::dev_alloc(d, bytes, &p); }
-  template <class T> T *as() const { return (T *)p; }
-};
-
 }  // namespace
 
 extern "C" int spring_fastq_reorder(const uint8_t *fastq, size_t nbytes, const uint32_t *order, uint32_t n,
@@ -91,13 +77,12 @@ extern "C" int spring_fastq_reorder(const uint8_t *fastq, size_t nbytes, const u
   HIPCHK(sr::excl_scan_u32_to_u64(st, nullptr, t2, nullptr, nullptr, (size_t)n + 1));
   tb = tb > t2 ? tb : t2;
   HIPCHK(tmp.alloc(dev, tb + 16));
-  hipEvent_t e0, e1;
-  HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-  struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evg{e0, e1};
+  Events ev;
+  HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b));
   HIPCHK(hipMemcpyAsync(txt.p, fastq, nbytes, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemcpyAsync(dorder.p, order, (size_t)n * 4, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(derr.p, 0, 4, st));
-  HIPCHK(hipEventRecord(e0, st));
+  HIPCHK(hipEventRecord(ev.a, st));
   sr::launch_nl_count(st, txt.as<uint8_t>(), nbytes, blk_cnt.as<uint32_t>(), nblk);
   t2 = tb;
   HIPCHK(sr::excl_scan_u32_to_u64(st, tmp.p, t2, blk_cnt.as<uint32_t>(), blk_off.as<uint64_t>(), nblk));
@@ -134,11 +119,11 @@ extern "C" int spring_fastq_reorder(const uint8_t *fastq, size_t nbytes, const u
   HIPCHK(dout.alloc(dev, total + 16));
   hipLaunchKernelGGL(k_copy_records, dim3((n + 3) / 4), dim3(256), 0, st, txt.as<uint8_t>(), le.as<uint64_t>(),
                      dorder.as<uint32_t>(), n, nrec, (uint64_t)nbytes, off.as<uint64_t>(), dout.as<uint8_t>());
-  HIPCHK(hipEventRecord(e1, st));
+  HIPCHK(hipEventRecord(ev.b, st));
   HIPCHK(hipMemcpyAsync(out, dout.p, total, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+  HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
   if (kernel_ms) *kernel_ms = ms;
   return 0;
 }

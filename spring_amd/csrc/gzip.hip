@@ -23,15 +23,9 @@
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_gzip.h"
+#include "stage_host.h"
 
-using sr::fail;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+using namespace sr;
 
 namespace {
 
@@ -45,24 +39,6 @@ constexpr uint32_t F_FIRST = 1, F_LAST = 2, F_STORED = 4;
 constexpr uint64_t BATCH_TOKEN_BYTES = 1ull << 30;   // token scratch of one batch of chunks
 constexpr int EMIT_T = 256;
 constexpr int STAGE_WORDS = EMIT_T * 48 / 32 + 4;
-
-struct DBuf {
-  int dev = 0;
-  void *p = nullptr;
-  DBuf() = default;
-  DBuf(const DBuf &) = delete;
-  DBuf &operator=(const DBuf &) = delete;
-  ~DBuf() { release(); }
-  void release() { if (p) { sr::dev_free(dev, p); p = nullptr; } }
-  hipError_t alloc(int d, size_t bytes) { release(); dev = d; return sr::dev_alloc(d, bytes, &p); }
-  template <class T> T *as() const { return (T *)p; }
-};
-#define DALLOC(buf, bytes) HIPCHK((buf).alloc(dev, (bytes) ? (bytes) : 16))
-
-inline dim3 grid(uint64_t n, uint32_t per_block = 256) {
-  const uint64_t b = (n + per_block - 1) / per_block;
-  return dim3((unsigned)(b ? b : 1));
-}
 
 __host__ __device__ inline uint32_t stored_size(uint32_t len) { return len + 5 * ((len + STORED_MAX - 1) / STORED_MAX); }
 
@@ -501,15 +477,6 @@ __global__ __launch_bounds__(256) void k_compact(CompactArg A) {
 }
 
 // ------------------------------------------------------------------ host side
-hipError_t rd(hipStream_t st, void *dst, const void *src, size_t n) {
-  hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st);
-  return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
-struct Events {
-  hipEvent_t e[8] = {};
-  ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
 
 }  // namespace
 
@@ -554,10 +521,7 @@ int compress(spring_gzip_ctx *ctx, const uint8_t *t, uint64_t nbytes, const uint
   for (auto &e : ev.e) HIPCHK(hipEventCreate(&e));
   DBuf moff, cnt, tmp, b_start, b_len, b_member, b_flags, b_payload, b_crc, b_ntok, b_hbits, b_carry, slots, tokens, codes,
       seg, m_crc, m_isize, b_slotoff;
-  struct SyncOnExit {   // declared behind the buffers: whatever is in flight ends before they go back to the pool
-    hipStream_t st;
-    ~SyncOnExit() { (void)hipStreamSynchronize(st); }
-  } sync_on_exit{st};
+  SyncOnExit sync_on_exit{st};
   HIPCHK(hipEventRecord(ev.e[0], st));
   // ---- cuts, chunk table
   DALLOC(moff, (M + 1) * 8);
@@ -686,23 +650,14 @@ int compress(spring_gzip_ctx *ctx, const uint8_t *t, uint64_t nbytes, const uint
   return 0;
 }
 
-int ctx_begin(spring_gzip_ctx *ctx) {
-  HIPCHK(hipSetDevice(ctx->dev));
-  if (!ctx->st) HIPCHK(hipStreamCreate(&ctx->st));
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
 
 int spring_gzip_create(int device, spring_gzip_ctx **out) {
   if (!out) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(SPRING_REORDER_E_HIP, "no HIP device available (the gzip stage has no CPU fallback)");
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-  if (device >= ndev) return fail(SPRING_REORDER_E_ARG, "device %d out of range", device);
+  const int r = stage_device(&device, "the gzip stage");
+  if (r) return r;
   spring_gzip_ctx *c = new spring_gzip_ctx();
   c->dev = device;
   memset(&c->info, 0, sizeof(c->info));
@@ -746,7 +701,7 @@ int spring_gzip_from_fastq_out(spring_gzip_ctx *ctx, spring_fastq_out_ctx *text,
   const uint64_t n = V.info.num_units;
   const uint64_t M = n == 0 ? 0 : member_records == 0 ? 1 : (n + member_records - 1) / member_records;
   if (M > 0xffffffffull) return fail(SPRING_REORDER_E_ARG, "too many members");
-  if ((r = ctx_begin(ctx))) return r;
+  if ((r = stream_begin(ctx->dev, &ctx->st))) return r;
   r = compress(ctx, V.text, V.info.bytes, V.rec_off, n, member_records == 0 ? n : member_records, nullptr, M, mode, info);
   if (ctx->st) (void)hipStreamSynchronize(ctx->st);
   if (r) drop_result(ctx);
@@ -767,7 +722,7 @@ int spring_gzip_from_host(spring_gzip_ctx *ctx, const uint8_t *bytes, uint64_t n
     return fail(SPRING_REORDER_E_ARG, "the member cuts do not start at 0 and end at the %llu bytes", (unsigned long long)nbytes);
   for (uint64_t m = 0; m < num_members; m++)
     if (member_off[m + 1] <= member_off[m]) return fail(SPRING_REORDER_E_ARG, "the member cuts do not increase strictly");
-  int r = ctx_begin(ctx);
+  int r = stream_begin(ctx->dev, &ctx->st);
   if (r) return r;
   const int dev = ctx->dev;
   DBuf up;
@@ -823,7 +778,7 @@ int spring_gzip_write(spring_gzip_ctx *ctx, const char *path, int32_t append, sp
   R.fd = fd;
   HIPCHK(hipSetDevice(ctx->dev));
   const uint64_t total = ctx->info.bytes_out, nchunk = (total + sr::PIN_CHUNK - 1) / sr::PIN_CHUNK;
-  if (nchunk) { const int r = ctx_begin(ctx); if (r) return r; }
+  if (nchunk) { const int r = stream_begin(ctx->dev, &ctx->st); if (r) return r; }
   for (int k = 0; k < 2 && (uint64_t)k < nchunk; k++) {
     if (!(R.pin[k] = sr::pinned_get())) return fail(SPRING_REORDER_E_HIP, "cannot pin a staging chunk for the members");
     HIPCHK(hipEventCreateWithFlags(&R.ev[k], hipEventDisableTiming));

@@ -22,15 +22,9 @@
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_idcodec.h"
+#include "stage_host.h"
 
-using sr::fail;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+using namespace sr;
 
 namespace {
 
@@ -56,24 +50,6 @@ constexpr uint32_t MAX_STEPS = 22, RENORM_BOUND = 26;
 inline uint64_t block_capacity(uint64_t symbols) {
   const uint64_t bytes = (MAX_STEPS * symbols + WORD_BITS) / 8 + 1;
   return ((bytes + 7) & ~7ull) + 8;   // whole 4-byte stores stay inside it
-}
-
-struct DBuf {
-  int dev = 0;
-  void *p = nullptr;
-  DBuf() = default;
-  DBuf(const DBuf &) = delete;
-  DBuf &operator=(const DBuf &) = delete;
-  ~DBuf() { release(); }
-  void release() { if (p) { sr::dev_free(dev, p); p = nullptr; } }
-  hipError_t alloc(int d, size_t bytes) { release(); dev = d; return sr::dev_alloc(d, bytes, &p); }
-  template <class T> T *as() const { return (T *)p; }
-};
-#define DALLOC(buf, bytes) HIPCHK((buf).alloc(dev, (bytes) ? (bytes) : 16))
-
-inline dim3 grid(uint64_t n, uint32_t per_block = 256) {
-  const uint64_t b = (n + per_block - 1) / per_block;
-  return dim3((unsigned)(b ? b : 1));
 }
 
 // ------------------------------------------------------------------ tokenizer
@@ -407,16 +383,6 @@ __global__ __launch_bounds__(256) void k_gather(const uint8_t *__restrict__ src,
   for (uint64_t i = blockIdx.y * 256ull + threadIdx.x; i < n; i += 256ull * gridDim.y) d[i] = s[i];
 }
 
-hipError_t rd(hipStream_t st, void *dst, const void *src, size_t n) {
-  hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st);
-  return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
-struct Events {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 }  // namespace
 
 struct spring_idcodec_ctx {
@@ -438,12 +404,6 @@ void drop_result(spring_idcodec_ctx *ctx) {
   ctx->out_off.clear();
   ctx->sym_off.clear();
   memset(&ctx->info, 0, sizeof(ctx->info));
-}
-
-int ctx_begin(spring_idcodec_ctx *ctx) {
-  HIPCHK(hipSetDevice(ctx->dev));
-  if (!ctx->st) HIPCHK(hipStreamCreate(&ctx->st));
-  return 0;
 }
 
 uint64_t workspace_need(uint64_t blocks, uint64_t max_tokens) { return blocks * (max_tokens + 1) * CTX_WORDS * 4; }
@@ -482,10 +442,7 @@ int run(spring_idcodec_ctx *ctx, const uint8_t *d_lines, uint64_t nbytes, const 
   Events ev;
   HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b));
   DBuf len1, loff, cnt, soff, tmp, stat, d_blk, d_cap, d_len_out, d_out_off, tables, flag, cap_buf;
-  struct SyncOnExit {   // declared behind the buffers: whatever is in flight ends before they go back to the pool
-    hipStream_t st;
-    ~SyncOnExit() { (void)hipStreamSynchronize(st); }
-  } sync_on_exit{st};
+  SyncOnExit sync_on_exit{st};
   float ms = 0;
   // ---- tokens, pass 1
   size_t tb = 0;
@@ -606,11 +563,8 @@ extern "C" {
 
 int spring_idcodec_create(int device, spring_idcodec_ctx **out) {
   if (!out) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(SPRING_REORDER_E_HIP, "no HIP device available (the id codec stage has no CPU fallback)");
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-  if (device >= ndev) return fail(SPRING_REORDER_E_ARG, "device %d out of range", device);
+  const int r = stage_device(&device, "the id codec stage");
+  if (r) return r;
   spring_idcodec_ctx *c = new spring_idcodec_ctx();
   c->dev = device;
   memset(&c->info, 0, sizeof(c->info));
@@ -645,7 +599,7 @@ int spring_idcodec_from_qualid(spring_idcodec_ctx *ctx, spring_qualid_ctx *q, sp
   if (!V.have[SPRING_QUALID_ID]) return fail(SPRING_REORDER_E_STATE, "the quality / id context holds no id result");
   if (V.dev != ctx->dev) return fail(SPRING_REORDER_E_ARG, "quality / id and id codec contexts live on different devices");
   if (V.num_reads_per_block == 0) return fail(SPRING_REORDER_E_ARG, "num_reads_per_block must be positive");
-  if ((r = ctx_begin(ctx))) return r;
+  if ((r = stream_begin(ctx->dev, &ctx->st))) return r;
   r = run(ctx, V.bytes[SPRING_QUALID_ID], V.info.bytes[SPRING_QUALID_ID], V.len[SPRING_QUALID_ID], V.info.num_units,
           V.num_reads_per_block, info);
   if (ctx->st) (void)hipStreamSynchronize(ctx->st);
@@ -674,7 +628,7 @@ int spring_idcodec_from_host(spring_idcodec_ctx *ctx, const uint8_t *lines, uint
   if (len.size() != num_lines)
     return fail(SPRING_REORDER_E_ARG, "the ids hold %llu lines, num_lines is %llu", (unsigned long long)len.size(), (unsigned long long)num_lines);
   len.push_back(0);
-  int r = ctx_begin(ctx);
+  int r = stream_begin(ctx->dev, &ctx->st);
   if (r) return r;
   const int dev = ctx->dev;
   DBuf up, d_len;

@@ -11,18 +11,9 @@
 #include "encoder_internal.h"
 #include "reorder_device.h"
 #include "spring_reorder.h"
+#include "stage_host.h"
 
-namespace sr {
-int fail(int code, const char *fmt, ...);
-}
-using sr::fail;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+using namespace sr;
 
 namespace {
 
@@ -71,11 +62,6 @@ struct Buf {
   hipError_t alloc(size_t b) { return hipMalloc(&p, b ? b : 16); }
   template <class T> T *as() { return (T *)p; }
 };
-struct Ev {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~Ev() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-inline dim3 grid(uint64_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 }  // namespace
 
@@ -85,7 +71,7 @@ int spring_order_invert_se(const uint32_t *order, uint32_t n, uint32_t *order_ar
   if (n && (!order || !order_array)) return fail(SPRING_REORDER_E_ARG, "NULL argument");
   if (kernel_ms) *kernel_ms = 0;
   if (!n) return 0;
-  Buf din, dout; Ev ev;
+  Buf din, dout; Events ev;
   HIPCHK(din.alloc((size_t)n * 4)); HIPCHK(dout.alloc((size_t)n * 4));
   HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b));
   HIPCHK(hipMemcpy(din.p, order, (size_t)n * 4, hipMemcpyHostToDevice));
@@ -104,7 +90,7 @@ int spring_order_invert_pe(const uint32_t *order, uint32_t n, uint32_t *order_ar
   if (kernel_ms) *kernel_ms = 0;
   if (!n) return 0;
   const uint32_t half = n / 2;
-  Buf din, dflag, dpos, dout, dtmp; Ev ev;
+  Buf din, dflag, dpos, dout, dtmp; Events ev;
   HIPCHK(din.alloc((size_t)n * 4)); HIPCHK(dflag.alloc((size_t)n * 4)); HIPCHK(dpos.alloc((size_t)n * 4));
   HIPCHK(dout.alloc((size_t)half * 4));
   HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b));
@@ -134,7 +120,7 @@ int spring_order_correct(uint32_t *order, uint64_t m, const uint32_t *order_N, u
   if (total64 > 4294967290ull) return fail(SPRING_REORDER_E_ARG, "too many reads");
   const uint32_t total = (uint32_t)total64;
   if (!m || !total) return 0;
-  Buf dord, dN, dflag, dnb, dcum, dtmp; Ev ev;
+  Buf dord, dN, dflag, dnb, dcum, dtmp; Events ev;
   HIPCHK(dord.alloc(m * 4)); HIPCHK(dN.alloc((size_t)nN * 4)); HIPCHK(dflag.alloc((size_t)total * 4));
   HIPCHK(dnb.alloc((size_t)total * 4)); HIPCHK(dcum.alloc((size_t)(n_clean ? n_clean : 1) * 4));
   HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b));
@@ -190,7 +176,7 @@ int spring_order_pe_encode(const uint32_t *order, uint32_t n, uint32_t *new_orde
   if (!n) return 0;
   if (n & 1) return fail(SPRING_REORDER_E_ARG, "pe_encode needs an even number of reads (pairs)");
   const uint32_t half = n / 2;
-  Buf din, dinv, dflag, drank, dout, dtmp; Ev ev;
+  Buf din, dinv, dflag, drank, dout, dtmp; Events ev;
   HIPCHK(din.alloc((size_t)n * 4)); HIPCHK(dinv.alloc((size_t)n * 4)); HIPCHK(dflag.alloc((size_t)n * 4));
   HIPCHK(drank.alloc((size_t)n * 4)); HIPCHK(dout.alloc((size_t)n * 4));
   HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b));

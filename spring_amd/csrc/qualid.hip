@@ -21,15 +21,9 @@
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_qualid.h"
+#include "stage_host.h"
 
-using sr::fail;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+using namespace sr;
 
 namespace {
 
@@ -40,24 +34,6 @@ constexpr uint32_t ERR_PERM = 1, ERR_QLEN = 2, ERR_LONG = 4, ERR_BYTE = 8;
 constexpr int COPY_BLOCK_BYTES = 4096;   // 256 lanes x 16 bytes
 constexpr int LDS_SLOTS = 1024;          // slot offsets of a copy block held in LDS (more: searched in memory)
 constexpr int CHANGED_SLOTS = 1024;      // counters the copy's blocks spread their bytes_changed over
-
-struct DBuf {
-  int dev = 0;
-  void *p = nullptr;
-  DBuf() = default;
-  DBuf(const DBuf &) = delete;
-  DBuf &operator=(const DBuf &) = delete;
-  ~DBuf() { release(); }
-  void release() { if (p) { sr::dev_free(dev, p); p = nullptr; } }
-  hipError_t alloc(int d, size_t bytes) { release(); dev = d; return sr::dev_alloc(d, bytes, &p); }
-  template <class T> T *as() const { return (T *)p; }
-};
-#define DALLOC(buf, bytes) HIPCHK((buf).alloc(dev, (bytes) ? (bytes) : 16))
-
-inline dim3 grid(uint64_t n, uint32_t per_block = 256) {
-  const uint64_t b = (n + per_block - 1) / per_block;
-  return dim3((unsigned)(b ? b : 1));
-}
 
 // ------------------------------------------------------------------ order -> the line of every slot
 __global__ void k_perm_check(const uint32_t *__restrict__ order, uint32_t n, uint32_t *__restrict__ hits,
@@ -292,10 +268,6 @@ __global__ void k_id_check(const uint8_t *__restrict__ t1, const uint64_t *__res
 }
 
 // ------------------------------------------------------------------ host side
-hipError_t rd(hipStream_t st, void *dst, const void *src, size_t n) {
-  hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st);
-  return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
 
 // A text in HBM with its newline index: line_end[j] = position of the '\n' of line j, nbytes for an unterminated
 // last line.  The buffer is padded so that the aligned 16-byte loads of the copy stay inside it.
@@ -335,11 +307,6 @@ int index_text(int dev, hipStream_t st, const uint8_t *text, size_t nbytes, Text
   return 0;
 }
 
-struct Events {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 }  // namespace
 
 struct spring_qualid_ctx {
@@ -363,12 +330,6 @@ void drop_results(spring_qualid_ctx *ctx) {
   ctx->have = false;
   for (int k = 0; k < 2; k++) { ctx->have_kind[k] = false; ctx->out[k].release(); ctx->len[k].release(); ctx->table[k].clear(); }
   memset(&ctx->info, 0, sizeof(ctx->info));
-}
-
-int ctx_begin(spring_qualid_ctx *ctx) {
-  HIPCHK(hipSetDevice(ctx->dev));
-  if (!ctx->st) HIPCHK(hipStreamCreate(&ctx->st));
-  return 0;
 }
 
 // d_order: device, num_reads entries, or null (identity)
@@ -548,11 +509,8 @@ extern "C" {
 
 int spring_qualid_create(int device, spring_qualid_ctx **out) {
   if (!out) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(SPRING_REORDER_E_HIP, "no HIP device available (the quality / id stage has no CPU fallback)");
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-  if (device >= ndev) return fail(SPRING_REORDER_E_ARG, "device %d out of range", device);
+  const int r = stage_device(&device, "the quality / id stage");
+  if (r) return r;
   spring_qualid_ctx *c = new spring_qualid_ctx();
   c->dev = device;
   memset(&c->info, 0, sizeof(c->info));
@@ -572,7 +530,7 @@ void spring_qualid_destroy(spring_qualid_ctx *ctx) {
 
 int spring_qualid_order_from_host(spring_qualid_ctx *ctx, const uint32_t *order, uint32_t num_reads, int32_t paired_end) {
   if (!ctx) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int r = ctx_begin(ctx);
+  int r = stream_begin(ctx->dev, &ctx->st);
   if (r) return r;
   const int dev = ctx->dev;
   DBuf d_order;
@@ -592,7 +550,7 @@ int spring_qualid_order_from_encoder(spring_qualid_ctx *ctx, spring_encoder_ctx 
   int r = sr::encoder_view(enc, &V);
   if (r) return r;
   if (V.dev != ctx->dev) return fail(SPRING_REORDER_E_ARG, "encoder and quality / id contexts live on different devices");
-  if ((r = ctx_begin(ctx))) return r;
+  if ((r = stream_begin(ctx->dev, &ctx->st))) return r;
   if (V.info.n_total != num_reads) {
     ctx->have_order = false;
     drop_results(ctx);
@@ -607,7 +565,7 @@ int spring_qualid_order_from_encoder(spring_qualid_ctx *ctx, spring_encoder_ctx 
 int spring_qualid_from_fastq(spring_qualid_ctx *ctx, const uint8_t *fastq, size_t nbytes, int32_t want,
                              const uint8_t *table, uint32_t num_reads_per_block, spring_qualid_info *info) {
   if (!ctx || (nbytes && !fastq)) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int r = ctx_begin(ctx);
+  int r = stream_begin(ctx->dev, &ctx->st);
   if (r) return r;
   drop_results(ctx);
   if (!ctx->have_order) return fail(SPRING_REORDER_E_STATE, "no order set (spring_qualid_order_from_host / _from_encoder)");
@@ -622,7 +580,7 @@ int spring_qualid_from_fastq(spring_qualid_ctx *ctx, const uint8_t *fastq, size_
 int spring_qualid_from_lines(spring_qualid_ctx *ctx, int32_t kind, const uint8_t *lines, size_t nbytes,
                              const uint8_t *table, uint32_t num_reads_per_block, spring_qualid_info *info) {
   if (!ctx || (nbytes && !lines)) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int r = ctx_begin(ctx);
+  int r = stream_begin(ctx->dev, &ctx->st);
   if (r) return r;
   drop_results(ctx);
   if (!ctx->have_order) return fail(SPRING_REORDER_E_STATE, "no order set (spring_qualid_order_from_host / _from_encoder)");
@@ -679,12 +637,8 @@ int spring_id_pattern(const uint8_t *fastq_1, size_t nbytes_1, const uint8_t *fa
   std::vector<uint8_t> unz[2];
   int r = sr::gunzip_if_needed(fastq_1, nbytes_1, unz[0]);
   if (!r) r = sr::gunzip_if_needed(fastq_2, nbytes_2, unz[1]);
+  if (!r) r = stage_device(&device, "the id check");
   if (r) return r;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(SPRING_REORDER_E_HIP, "no HIP device available (the id check has no CPU fallback)");
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-  if (device >= ndev) return fail(SPRING_REORDER_E_ARG, "device %d out of range", device);
   const int dev = device;
   HIPCHK(hipSetDevice(dev));
   hipStream_t st = nullptr;   // the null stream

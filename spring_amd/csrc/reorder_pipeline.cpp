@@ -32,6 +32,7 @@
 #include "dict_build.h"
 #include "reorder_internal.h"
 #include "spring_reorder.h"
+#include "stage_host.h"
 #include "synth_common.h"
 
 namespace sr {
@@ -48,13 +49,6 @@ int fail(int code, const char *fmt, ...) {
 }  // namespace sr
 
 using namespace sr;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
 // ---------------------------------------------------------------- device pool
 // hipMalloc/hipFree of the ~30 GB a 100 M-read run needs cost ~1 s per run, as much as

@@ -1,0 +1,82 @@
+// spring_amd/csrc/stage_host.h -- the host-side frame that every stage context shares: the HIP
+// error check, pooled device buffers, launch grids, event holders and the device / stream set-up of a context.  Host
+// code only; a stage writes its kernels, its context struct, its drop_result / destroy and its entry points itself.
+// Internal to the library.
+#ifndef SPRING_STAGE_HOST_H_
+#define SPRING_STAGE_HOST_H_
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include "reorder_internal.h"
+
+// A macro, so that the file and the line are the caller's.  Needs `fail` in scope (using sr::fail, or namespace sr).
+#define HIPCHK(x)                                                                              \
+  do {                                                                                         \
+    hipError_t e_ = (x);                                                                       \
+    if (e_ != hipSuccess)                                                                      \
+      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
+  } while (0)
+
+namespace sr {
+
+// A device buffer from the library's pool (dev_alloc hands out at least 16 bytes, so a size of 0 is fine).
+struct DBuf {
+  int dev = 0;
+  void *p = nullptr;
+  DBuf() = default;
+  DBuf(const DBuf &) = delete;
+  DBuf &operator=(const DBuf &) = delete;
+  ~DBuf() { release(); }
+  void release() { if (p) { dev_free(dev, p); p = nullptr; } }
+  hipError_t alloc(int d, size_t bytes) { release(); dev = d; return dev_alloc(d, bytes, &p); }
+  template <class T> T *as() const { return (T *)p; }
+};
+// Needs `dev` in scope.
+#define DALLOC(buf, bytes) HIPCHK((buf).alloc(dev, (bytes)))
+
+// Blocks for n items; never zero, so a launch over nothing is still a valid launch.
+inline dim3 grid(uint64_t n, uint32_t per_block = 256) {
+  const uint64_t b = (n + per_block - 1) / per_block;
+  return dim3((unsigned)(b ? b : 1));
+}
+
+// Device to host, done when it returns.
+inline hipError_t rd(hipStream_t st, void *dst, const void *src, size_t n) {
+  hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st);
+  return e != hipSuccess ? e : hipStreamSynchronize(st);
+}
+
+// Up to eight events, destroyed with the holder; a and b name the first two for a function that times one span.
+struct Events {
+  hipEvent_t e[8] = {};
+  hipEvent_t &a = e[0], &b = e[1];
+  ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+// Declare it behind the buffers of a function: whatever is in flight ends before they go back to the pool.
+struct SyncOnExit {
+  hipStream_t st;
+  ~SyncOnExit() { (void)hipStreamSynchronize(st); }
+};
+
+// The device of a new context: *device < 0 picks the current one.  `what` names the stage in the message.
+inline int stage_device(int *device, const char *what) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return fail(SPRING_REORDER_E_HIP, "no HIP device available (%s has no CPU fallback)", what);
+  if (*device < 0 && hipGetDevice(device) != hipSuccess) *device = 0;
+  if (*device >= ndev) return fail(SPRING_REORDER_E_ARG, "device %d out of range", *device);
+  return 0;
+}
+
+// What every entry point that touches the device starts with: the context's device, and its stream on first use.
+inline int stream_begin(int dev, hipStream_t *st) {
+  HIPCHK(hipSetDevice(dev));
+  if (!*st) HIPCHK(hipStreamCreate(st));
+  return 0;
+}
+
+}  // namespace sr
+#endif

@@ -29,16 +29,10 @@
 #include "reorder_device.h"
 #include "reorder_internal.h"
 #include "spring_streams.h"
+#include "stage_host.h"
 #include "streams_internal.h"
 
-using sr::fail;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+using namespace sr;
 
 namespace {
 
@@ -59,24 +53,6 @@ __host__ __device__ inline int var_stream(int v) {
 
 // error bits of the device checks
 constexpr uint32_t ERR_PERM = 1, ERR_UNREC = 2, ERR_CODE = 4;
-
-struct DBuf {
-  int dev = 0;
-  void *p = nullptr;
-  DBuf() = default;
-  DBuf(const DBuf &) = delete;
-  DBuf &operator=(const DBuf &) = delete;
-  ~DBuf() { release(); }
-  void release() { if (p) { sr::dev_free(dev, p); p = nullptr; } }
-  hipError_t alloc(int d, size_t bytes) { release(); dev = d; return sr::dev_alloc(d, bytes, &p); }
-  template <class T> T *as() const { return (T *)p; }
-};
-#define DALLOC(buf, bytes) HIPCHK((buf).alloc(dev, (bytes) ? (bytes) : 16))
-
-inline dim3 grid(uint64_t n, uint32_t per_block = 256) {
-  const uint64_t b = (n + per_block - 1) / per_block;
-  return dim3((unsigned)(b ? b : 1));
-}
 
 // ------------------------------------------------------------------ index
 __global__ void k_nl_flag(const char *__restrict__ noise, uint64_t nb, uint32_t *__restrict__ f) {
@@ -370,11 +346,6 @@ int check_params(uint64_t n_total, uint32_t N, int pe, uint32_t B) {
   return 0;
 }
 
-hipError_t rd(hipStream_t st, void *dst, const void *src, size_t n) {
-  hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st);
-  return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
 int run_core(spring_streams_ctx *ctx, const In &I, uint32_t N, bool pe, bool po, uint32_t B, spring_streams_info *info_out) {
   const int dev = ctx->dev;
   hipStream_t st = ctx->st;
@@ -520,24 +491,14 @@ int run_core(spring_streams_ctx *ctx, const In &I, uint32_t N, bool pe, bool po,
   return 0;
 }
 
-int ctx_begin(spring_streams_ctx *ctx) {
-  HIPCHK(hipSetDevice(ctx->dev));
-  if (!ctx->st) HIPCHK(hipStreamCreate(&ctx->st));
-  ctx->have = false;
-  return 0;
-}
-
 }  // namespace
 
 extern "C" {
 
 int spring_streams_create(int device, spring_streams_ctx **out) {
   if (!out) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(SPRING_REORDER_E_HIP, "no HIP device available (the streams stage has no CPU fallback)");
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-  if (device >= ndev) return fail(SPRING_REORDER_E_ARG, "device %d out of range", device);
+  const int r = stage_device(&device, "the streams stage");
+  if (r) return r;
   spring_streams_ctx *c = new spring_streams_ctx();
   c->dev = device;
   memset(&c->info, 0, sizeof(c->info));
@@ -565,7 +526,8 @@ int spring_streams_from_encoder(spring_streams_ctx *ctx, spring_encoder_ctx *enc
   if ((r = check_params(V.info.n_total, num_reads, paired_end, num_reads_per_block))) return r;
   if (apply_pe_encode && (!paired_end || preserve_order))
     return fail(SPRING_REORDER_E_ARG, "apply_pe_encode is for paired-end data without preserve_order");
-  if ((r = ctx_begin(ctx))) return r;
+  if ((r = stream_begin(ctx->dev, &ctx->st))) return r;
+  ctx->have = false;
   const int dev = ctx->dev;
   In I;
   I.pos = V.pos; I.rc = V.rc; I.noise = V.noise; I.noisepos = V.noisepos; I.rlen = V.rlen; I.un = V.unaligned;
@@ -604,7 +566,8 @@ int spring_streams_from_host(spring_streams_ctx *ctx, const uint64_t *pos, const
   if ((n_aligned && (!pos || !rc)) || (noise_bytes && !noise) || (n_noisepos && !noisepos) || (n_total && !rlen) ||
       (unaligned_bytes && !unaligned) || (use_order && n_total && !order))
     return fail(SPRING_REORDER_E_ARG, "NULL stream");
-  if ((r = ctx_begin(ctx))) return r;
+  if ((r = stream_begin(ctx->dev, &ctx->st))) return r;
+  ctx->have = false;
   const int dev = ctx->dev;
   hipStream_t st = ctx->st;
   DBuf d_pos, d_rc, d_noise, d_np, d_order, d_rlen, d_un;

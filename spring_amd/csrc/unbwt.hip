@@ -22,39 +22,15 @@
 #include "bwt_internal.h"
 #include "reorder_internal.h"
 #include "spring_unbwt.h"
+#include "stage_host.h"
 #include "unbwt_plan.h"
 
-using sr::fail;
-
-#define HIPCHK(x)                                                                              \
-  do {                                                                                         \
-    hipError_t e_ = (x);                                                                       \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(SPRING_REORDER_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
+using namespace sr;
 
 namespace {
 
 constexpr uint64_t SORT_FIXED_BYTES = 8ull << 20;   // the sort's tables that do not grow with the input
 constexpr int NPASS = SPRING_UNBWT_PASSES;
-
-struct DBuf {
-  int dev = 0;
-  void *p = nullptr;
-  DBuf() = default;
-  DBuf(const DBuf &) = delete;
-  DBuf &operator=(const DBuf &) = delete;
-  ~DBuf() { release(); }
-  void release() { if (p) { sr::dev_free(dev, p); p = nullptr; } }
-  hipError_t alloc(int d, size_t bytes) { release(); dev = d; return sr::dev_alloc(d, bytes, &p); }
-  template <class T> T *as() const { return (T *)p; }
-};
-#define DALLOC(buf, bytes) HIPCHK((buf).alloc(dev, (bytes) ? (bytes) : 16))
-
-inline dim3 grid(uint64_t n, uint32_t per_block = 256) {
-  const uint64_t b = (n + per_block - 1) / per_block;
-  return dim3((unsigned)(b ? b : 1));
-}
 
 // A sub-batch: segments [first, first + count) of the batch; byte p of it is byte off[first] + p of the batch.
 struct Sub {
@@ -298,16 +274,6 @@ hipError_t sort_words(hipStream_t st, void *tmp, size_t &tmp_bytes, const uint64
       tmp, tmp_bytes, in, out, n, 32u, end_bit, st);
 }
 
-hipError_t rd(hipStream_t st, void *dst, const void *src, size_t n) {
-  hipError_t e = hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, st);
-  return e != hipSuccess ? e : hipStreamSynchronize(st);
-}
-
-struct Events {
-  hipEvent_t e[8] = {};
-  ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-
 }  // namespace
 
 struct spring_unbwt_ctx {
@@ -328,12 +294,6 @@ void drop_result(spring_unbwt_ctx *ctx) {
   ctx->out.release();
   ctx->off.clear();
   memset(&ctx->info, 0, sizeof(ctx->info));
-}
-
-int ctx_begin(spring_unbwt_ctx *ctx) {
-  HIPCHK(hipSetDevice(ctx->dev));
-  if (!ctx->st) HIPCHK(hipStreamCreate(&ctx->st));
-  return 0;
 }
 
 struct Work {   // the arrays of a sub-batch, sized for the largest one
@@ -456,10 +416,7 @@ int invert(spring_unbwt_ctx *ctx, const std::vector<uint64_t> &src, const int32_
     hmax = std::max(hmax, unbwt::regular_heads(m + k, ctx->log_k) + 2 * k);
   }
   Work W;
-  struct SyncOnExit {   // declared behind the buffers: whatever is in flight ends before they go back to the pool
-    hipStream_t st;
-    ~SyncOnExit() { (void)hipStreamSynchronize(st); }
-  } sync_on_exit{st};
+  SyncOnExit sync_on_exit{st};
   if (mmax) {
     size_t tb = 0;
     HIPCHK(sort_words(st, nullptr, tb, nullptr, nullptr, mmax, 64));
@@ -508,11 +465,8 @@ extern "C" {
 
 int spring_unbwt_create(int device, spring_unbwt_ctx **out) {
   if (!out) return fail(SPRING_REORDER_E_ARG, "NULL argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(SPRING_REORDER_E_HIP, "no HIP device available (the inverse block-sort stage has no CPU fallback)");
-  if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
-  if (device >= ndev) return fail(SPRING_REORDER_E_ARG, "device %d out of range", device);
+  const int r = stage_device(&device, "the inverse block-sort stage");
+  if (r) return r;
   spring_unbwt_ctx *c = new spring_unbwt_ctx();
   c->dev = device;
   memset(&c->info, 0, sizeof(c->info));
@@ -559,7 +513,7 @@ int spring_unbwt_from_host(spring_unbwt_ctx *ctx, const uint8_t *bytes, uint64_t
     return fail(SPRING_REORDER_E_ARG, "the segment offsets do not start at 0 and end at the %llu bytes", (unsigned long long)nbytes);
   for (uint64_t s = 0; s < num_segments; s++)
     if (seg_off[s + 1] < seg_off[s]) return fail(SPRING_REORDER_E_ARG, "the segment offsets decrease");
-  int r = ctx_begin(ctx);
+  int r = stream_begin(ctx->dev, &ctx->st);
   if (r) return r;
   const int dev = ctx->dev;
   DBuf up, d_prim;
@@ -584,7 +538,7 @@ int spring_unbwt_from_bwt(spring_unbwt_ctx *ctx, spring_bwt_ctx *bwt_ctx, spring
   int r = sr::bwt_view(bwt_ctx, &V);
   if (r) return r;
   if (V.dev != ctx->dev) return fail(SPRING_REORDER_E_ARG, "block-sort and inverse contexts live on different devices");
-  if ((r = ctx_begin(ctx))) return r;
+  if ((r = stream_begin(ctx->dev, &ctx->st))) return r;
   const uint64_t S = V.num_segments;
   std::vector<int32_t> prim(S ? S : 1);
   if (S) HIPCHK(rd(ctx->st, prim.data(), V.primary, S * 4));

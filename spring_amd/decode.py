@@ -6,47 +6,21 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .reorder import ReorderError
+from ._stage import Stage, chk
 from .streams import STREAM_FILES
 
 
-def _chk(rc):
-    if rc != 0:
-        raise ReorderError("%s (code %d)" % (_lib.lib().spring_reorder_last_error().decode(), rc))
-
-
-class DecodeStage:
+class DecodeStage(Stage):
     """seq_from_*() loads the consensus once; from_*() decodes a window of blocks into the reads of its units in slot
     order; download(mate) / reads(mate) fetch read 1 (mate 0) or read 2 (mate 1, paired-end)."""
 
-    def __init__(self, device: int = -1):
-        self._L = _lib.lib()
-        self._h = C.c_void_p()
-        _chk(self._L.spring_decode_create(device, C.byref(self._h)))
-        self.info = None
-
-    def close(self):
-        if self._h:
-            self._L.spring_decode_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _prefix, _Info = "spring_decode", _lib.DecodeInfo
 
     # ---- the consensus
     def seq_from_encoder(self, enc):
         """enc: an EncoderStage after encode(); its consensus is copied on the device."""
         self.info = None
-        _chk(self._L.spring_decode_seq_from_encoder(self._h, enc._h))
+        chk(self._L.spring_decode_seq_from_encoder(self._h, enc._h))
 
     def seq_from_host(self, seq_len_tid, packed, tails):
         """The images EncoderStage.seq_packed() gives: seq_len_tid, packed bytes (tid-major), a tail string per tid."""
@@ -58,22 +32,18 @@ class DecodeStage:
             b = s.encode() if isinstance(s, str) else bytes(s)
             tail[4 * t:4 * t + len(b)] = np.frombuffer(b, np.uint8)
         buf = np.frombuffer(bytes(packed), np.uint8)
-        _chk(self._L.spring_decode_seq_from_host(self._h, T, sl.ctypes.data if T else None,
-                                                 buf.ctypes.data if len(buf) else None, tail.ctypes.data))
+        chk(self._L.spring_decode_seq_from_host(self._h, T, sl.ctypes.data if T else None,
+                                                buf.ctypes.data if len(buf) else None, tail.ctypes.data))
 
     def seq_from_files(self, temp_dir: str, num_thr_e: int):
         """temp_dir/read_seq.bin.<tid> (+ .tail) for tid < num_thr_e; removed on success."""
         self.info = None
-        _chk(self._L.spring_decode_seq_from_files(self._h, temp_dir.encode(), num_thr_e))
+        chk(self._L.spring_decode_seq_from_files(self._h, temp_dir.encode(), num_thr_e))
 
     # ---- the blocks
     def from_streams(self, ss):
         """Every block of the last run of a StreamsStage, with that run's parameters."""
-        info = _lib.DecodeInfo()
-        self.info = None
-        _chk(self._L.spring_decode_from_streams(self._h, ss._h, C.byref(info)))
-        self.info = info.asdict()
-        return self.info
+        return self._run("from_streams", ss._h)
 
     def from_host(self, streams, num_reads, paired_end=False, preserve_order=False, num_reads_per_block=256000,
                   first_block=0, num_blocks=None):
@@ -93,32 +63,23 @@ class DecodeStage:
             offs[sid] = o.ctypes.data
             if num_blocks is None:
                 num_blocks = len(o) - 1
-        info = _lib.DecodeInfo()
-        self.info = None
-        _chk(self._L.spring_decode_from_host(self._h, ptrs, offs, first_block, num_blocks or 0, num_reads,
-                                             int(paired_end), int(preserve_order), num_reads_per_block, C.byref(info)))
-        self.info = info.asdict()
-        return self.info
+        return self._run("from_host", ptrs, offs, first_block, num_blocks or 0, num_reads, int(paired_end),
+                         int(preserve_order), num_reads_per_block)
 
     def from_files(self, temp_dir: str, first_block, num_blocks, num_reads, paired_end=False, preserve_order=False,
                    num_reads_per_block=256000):
         """temp_dir/<stream>.<b> for the window's blocks; removed on success."""
-        info = _lib.DecodeInfo()
-        self.info = None
-        _chk(self._L.spring_decode_from_files(self._h, temp_dir.encode(), first_block, num_blocks, num_reads,
-                                              int(paired_end), int(preserve_order), num_reads_per_block,
-                                              C.byref(info)))
-        self.info = info.asdict()
-        return self.info
+        return self._run("from_files", temp_dir.encode(), first_block, num_blocks, num_reads, int(paired_end),
+                         int(preserve_order), num_reads_per_block)
 
     def download(self, mate=0):
         """-> (bases of the mate's reads back to back, num_units + 1 uint64 offsets)."""
         if self.info is None:   # nothing decoded (or the last call failed): the library says so
-            _chk(self._L.spring_decode_download(self._h, mate, None, None))
+            chk(self._L.spring_decode_download(self._h, mate, None, None))
         n = self.info["bases"][mate]
         buf = np.zeros(max(n, 1), np.uint8)
         off = np.zeros(self.info["num_units"] + 1, np.uint64)
-        _chk(self._L.spring_decode_download(self._h, mate, buf.ctypes.data, off.ctypes.data))
+        chk(self._L.spring_decode_download(self._h, mate, buf.ctypes.data, off.ctypes.data))
         return buf[:n].tobytes(), off
 
     def reads(self, mate=0):

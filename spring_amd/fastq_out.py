@@ -6,17 +6,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._stage import Stage, chk
 from .decode import DecodeStage
 from .qualid import QualIdStage
-from .reorder import ReorderError
 
 ID_STORED, ID_NUMBERED, ID_FROM_MATE_1 = 0, 1, 2
 TO_END = (1 << 64) - 1
-
-
-def _chk(rc):
-    if rc != 0:
-        raise ReorderError("%s (code %d)" % (_lib.lib().spring_reorder_last_error().decode(), rc))
 
 
 def _u8(b):
@@ -26,32 +21,11 @@ def _u8(b):
     return a, (a.ctypes.data if len(a) else None)
 
 
-class FastqOutStage:
+class FastqOutStage(Stage):
     """assemble(): the text `id\\nread\\n+\\nquality\\n` per unit of one mate over a window of blocks, in HBM;
     download() / write() fetch it."""
 
-    def __init__(self, device: int = -1):
-        self._L = _lib.lib()
-        self._h = C.c_void_p()
-        _chk(self._L.spring_fastq_out_create(device, C.byref(self._h)))
-        self.info = None
-
-    def close(self):
-        if self._h:
-            self._L.spring_fastq_out_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _prefix, _Info = "spring_fastq_out", _lib.FastqOutInfo
 
     def assemble(self, reads, num_reads, quality=None, ids=None, paired_end=False, num_reads_per_block=256000,
                  first_block=0, num_blocks=None, mate=0, preserve_id=True, paired_id_code=None, unit_range=None):
@@ -98,35 +72,31 @@ class FastqOutStage:
                 t = np.zeros(num_blocks + 1, np.uint64)
                 keep.append(t)
                 setattr(S, name + "_block_off", t.ctypes.data)
-        info = _lib.FastqOutInfo()
-        self.info = None
-        _chk(self._L.spring_fastq_out_assemble(self._h, C.byref(P), C.byref(S), C.byref(info)))
-        self.info = info.asdict()
-        return self.info
+        return self._run("assemble", C.byref(P), C.byref(S))
 
     def download(self, text=True, rec_off=True):
         """-> (the text: bytes, record offsets: num_units + 1 uint64); a part not asked for is None."""
         if self.info is None:   # nothing assembled (or the last call failed): the library says so
-            _chk(self._L.spring_fastq_out_download(self._h, None, None))
+            chk(self._L.spring_fastq_out_download(self._h, None, None))
         n = self.info["bytes"]
         buf = np.zeros(max(n, 1), np.uint8) if text else None
         off = np.zeros(self.info["num_units"] + 1, np.uint64) if rec_off else None
-        _chk(self._L.spring_fastq_out_download(self._h, buf.ctypes.data if text else None,
-                                               off.ctypes.data if rec_off else None))
+        chk(self._L.spring_fastq_out_download(self._h, buf.ctypes.data if text else None,
+                                              off.ctypes.data if rec_off else None))
         return (buf[:n].tobytes() if text else None), off
 
     def download_array(self):
         """-> the text as a uint8 array (no second copy on the host)."""
         if self.info is None:
-            _chk(self._L.spring_fastq_out_download(self._h, None, None))
+            chk(self._L.spring_fastq_out_download(self._h, None, None))
         n = self.info["bytes"]
         buf = np.zeros(max(n, 1), np.uint8)
-        _chk(self._L.spring_fastq_out_download(self._h, buf.ctypes.data, None))
+        chk(self._L.spring_fastq_out_download(self._h, buf.ctypes.data, None))
         return buf[:n]
 
     def write(self, path, append=False):
         """The text to a plain file (gzip output: GzipStage.compress(this stage)); -> info with ms_file."""
         info = _lib.FastqOutInfo()
-        _chk(self._L.spring_fastq_out_write(self._h, str(path).encode(), int(append), C.byref(info)))
+        chk(self._L.spring_fastq_out_write(self._h, str(path).encode(), int(append), C.byref(info)))
         self.info = info.asdict()
         return self.info

@@ -5,16 +5,11 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._stage import Stage, chk
 from .qualid import QualIdStage
-from .reorder import ReorderError
 
 KINDS = ("type", "alpha_len", "alpha_byte", "char", "delta", "zero_run", "integer")   # bits 8-10 of a symbol word
 TOKEN_TYPES = ("ALPHA", "DIGIT", "CHAR", "MATCH", "ZEROS", "DELTA", "END")            # the values of kind "type"
-
-
-def _chk(rc):
-    if rc != 0:
-        raise ReorderError("%s (code %d)" % (_lib.lib().spring_reorder_last_error().decode(), rc))
 
 
 def workspace_need(blocks, max_tokens):
@@ -22,46 +17,21 @@ def workspace_need(blocks, max_tokens):
     return int(_lib.lib().spring_idcodec_workspace_need(blocks, max_tokens))
 
 
-class IdCodecStage:
+class IdCodecStage(Stage):
     """from_qualid() / from_lines(): the id blocks of a run compressed on the device into the bytes compress_id_block
     writes to id_N.<block>.  blocks() fetches them, symbols() the token symbols the coder ran on."""
 
-    def __init__(self, device: int = -1):
-        self._L = _lib.lib()
-        self._h = C.c_void_p()
-        _chk(self._L.spring_idcodec_create(device, C.byref(self._h)))
-        self.info = None
-
-    def close(self):
-        if self._h:
-            self._L.spring_idcodec_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _prefix, _Info = "spring_idcodec", _lib.IdCodecInfo
 
     def set_workspace_bytes(self, workspace_bytes):
         """The device memory the model tables of a sub-batch may use (0: from the free HBM)."""
-        _chk(self._L.spring_idcodec_set_workspace_bytes(self._h, workspace_bytes))
+        chk(self._L.spring_idcodec_set_workspace_bytes(self._h, workspace_bytes))
 
     def from_qualid(self, qualid):
         """qualid: a QualIdStage holding an id result; it stays in HBM and is left as it was.  -> info."""
         if not isinstance(qualid, QualIdStage):
             raise TypeError("from_qualid takes a QualIdStage")
-        info = _lib.IdCodecInfo()
-        self.info = None
-        _chk(self._L.spring_idcodec_from_qualid(self._h, qualid._h, C.byref(info)))
-        self.info = info.asdict()
-        return self.info
+        return self._run("from_qualid", qualid._h)
 
     def from_lines(self, lines, num_reads_per_block=256000):
         """lines: a list of ids (bytes, without '\\n') in slot order, or their image with every id '\\n'-terminated.
@@ -72,21 +42,16 @@ class IdCodecStage:
             lines = lines.tobytes() if isinstance(lines, np.ndarray) else bytes(lines)
             n = lines.count(b"\n")
         a = np.frombuffer(lines, np.uint8)
-        info = _lib.IdCodecInfo()
-        self.info = None
-        _chk(self._L.spring_idcodec_from_host(self._h, a.ctypes.data if len(a) else None, len(a), n, num_reads_per_block,
-                                              C.byref(info)))
-        self.info = info.asdict()
-        return self.info
+        return self._run("from_host", a.ctypes.data if len(a) else None, len(a), n, num_reads_per_block)
 
     def download(self):
         """-> (bytes of all blocks back to back, block offsets: uint64)."""
         if self.info is None:   # nothing compressed (or the last call failed): the library says so
-            _chk(self._L.spring_idcodec_download(self._h, None, None))
+            chk(self._L.spring_idcodec_download(self._h, None, None))
         n = self.info["bytes"]
         buf = np.zeros(max(n, 1), np.uint8)
         off = np.zeros(self.info["num_blocks"] + 1, np.uint64)
-        _chk(self._L.spring_idcodec_download(self._h, buf.ctypes.data, off.ctypes.data))
+        chk(self._L.spring_idcodec_download(self._h, buf.ctypes.data, off.ctypes.data))
         return buf[:n].tobytes(), off
 
     def blocks(self):
@@ -97,15 +62,9 @@ class IdCodecStage:
     def symbols(self):
         """-> (symbol words: uint32, value | kind << 8 | context << 11; per-block offsets: uint64)."""
         if self.info is None:
-            _chk(self._L.spring_idcodec_symbols(self._h, None, None))
+            chk(self._L.spring_idcodec_symbols(self._h, None, None))
         n = self.info["num_symbols"]
         words = np.zeros(max(n, 1), np.uint32)
         off = np.zeros(self.info["num_blocks"] + 1, np.uint64)
-        _chk(self._L.spring_idcodec_symbols(self._h, words.ctypes.data, off.ctypes.data))
+        chk(self._L.spring_idcodec_symbols(self._h, words.ctypes.data, off.ctypes.data))
         return words[:n], off
-
-    def get_info(self):
-        """The info of the result the context holds (the library refuses when there is none)."""
-        info = _lib.IdCodecInfo()
-        _chk(self._L.spring_idcodec_get_info(self._h, C.byref(info)))
-        return info.asdict()

@@ -6,15 +6,10 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from .reorder import ReorderError
+from ._stage import ReorderError, Stage, chk
 
 QUALITY, ID = 0, 1
 KIND = {"quality": QUALITY, "id": ID, QUALITY: QUALITY, ID: ID}
-
-
-def _chk(rc):
-    if rc != 0:
-        raise ReorderError("%s (code %d)" % (_lib.lib().spring_reorder_last_error().decode(), rc))
 
 
 def _u8(b):
@@ -29,7 +24,7 @@ def quality_table(mode, thr=0, high=0, low=0):
     (byte < 33 + thr -> 33 + low, else 33 + high; util.cpp:182-188).  Host only."""
     m = {"illumina": 1, "ill_bin": 1, "binary": 2}.get(mode, mode)
     t = np.zeros(128, np.uint8)
-    _chk(_lib.lib().spring_quality_table(int(m), thr, high, low, t.ctypes.data))
+    chk(_lib.lib().spring_quality_table(int(m), thr, high, low, t.ctypes.data))
     return t
 
 
@@ -39,11 +34,11 @@ def id_pattern(fastq_1, fastq_2, device=-1):
     a, pa = _u8(fastq_1)
     b, pb = _u8(fastq_2)
     code, ms = C.c_uint8(0), C.c_double(0)
-    _chk(_lib.lib().spring_id_pattern(pa, len(a), pb, len(b), device, C.byref(code), C.byref(ms)))
+    chk(_lib.lib().spring_id_pattern(pa, len(a), pb, len(b), device, C.byref(code), C.byref(ms)))
     return int(code.value)
 
 
-class QualIdStage:
+class QualIdStage(Stage):
     """set_order() / set_order_from_encoder(), then from_fastq() / from_lines(): the quality lines and id lines of one
     input file in the final read order, cut into blocks of num_reads_per_block reads (pairs), on the device.
     download(kind) / blocks(kind) fetch a result."""
@@ -51,29 +46,11 @@ class QualIdStage:
     quality_table = staticmethod(quality_table)
     id_pattern = staticmethod(id_pattern)
 
+    _prefix, _Info = "spring_qualid", _lib.QualIdInfo
+
     def __init__(self, device: int = -1):
-        self._L = _lib.lib()
-        self._h = C.c_void_p()
-        _chk(self._L.spring_qualid_create(device, C.byref(self._h)))
-        self.info = None
+        super().__init__(device)
         self._B = 0
-
-    def close(self):
-        if self._h:
-            self._L.spring_qualid_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def set_order(self, order, num_reads, paired_end=False):
         """order: the image of read_order.bin before pe_encode (num_reads entries), or None for the identity
@@ -83,13 +60,13 @@ class QualIdStage:
             order = np.ascontiguousarray(order, dtype=np.uint32)
             if len(order) != num_reads:
                 raise ReorderError("order holds %d entries, num_reads is %d" % (len(order), num_reads))
-        _chk(self._L.spring_qualid_order_from_host(self._h, None if order is None or not len(order) else order.ctypes.data,
-                                                   num_reads, int(paired_end)))
+        chk(self._L.spring_qualid_order_from_host(self._h, None if order is None or not len(order) else order.ctypes.data,
+                                                  num_reads, int(paired_end)))
 
     def set_order_from_encoder(self, enc, num_reads, paired_end=False):
         """enc: an EncoderStage after encode(); its order stays in HBM and is left as it was."""
         self.info = None
-        _chk(self._L.spring_qualid_order_from_encoder(self._h, enc._h, num_reads, int(paired_end)))
+        chk(self._L.spring_qualid_order_from_encoder(self._h, enc._h, num_reads, int(paired_end)))
 
     def from_fastq(self, fastq, want=("quality", "id"), table=None, num_reads_per_block=256000):
         """fastq: the text (or gzip image) of one input file.  want: the kinds to build.  table: 128 bytes or None."""
@@ -98,10 +75,8 @@ class QualIdStage:
         t, pt = (None, None) if table is None else _u8(table)
         if t is not None and len(t) != 128:
             raise ReorderError("the quality table has 128 entries")
-        info = _lib.QualIdInfo()
-        self.info = None
-        _chk(self._L.spring_qualid_from_fastq(self._h, pa, len(a), bits, pt, num_reads_per_block, C.byref(info)))
-        self.info, self._B = info.asdict(), num_reads_per_block
+        self._run("from_fastq", pa, len(a), bits, pt, num_reads_per_block)
+        self._B = num_reads_per_block
         return self.info
 
     def from_lines(self, kind, lines, table=None, num_reads_per_block=256000):
@@ -110,22 +85,20 @@ class QualIdStage:
         t, pt = (None, None) if table is None else _u8(table)
         if t is not None and len(t) != 128:
             raise ReorderError("the quality table has 128 entries")
-        info = _lib.QualIdInfo()
-        self.info = None
-        _chk(self._L.spring_qualid_from_lines(self._h, KIND[kind], pa, len(a), pt, num_reads_per_block, C.byref(info)))
-        self.info, self._B = info.asdict(), num_reads_per_block
+        self._run("from_lines", KIND[kind], pa, len(a), pt, num_reads_per_block)
+        self._B = num_reads_per_block
         return self.info
 
     def download(self, kind):
         """-> (bytes of all blocks back to back, line lengths in slot order: uint32, block offsets: uint64)."""
         k = KIND[kind]
         if self.info is None:   # nothing computed (or the last call failed): the library says so
-            _chk(self._L.spring_qualid_download(self._h, k, None, None, None))
+            chk(self._L.spring_qualid_download(self._h, k, None, None, None))
         n = self.info["bytes"][k]
         buf = np.zeros(max(n, 1), np.uint8)
         ln = np.zeros(max(self.info["num_units"], 1), np.uint32)
         off = np.zeros(self.info["num_blocks"] + 1, np.uint64)
-        _chk(self._L.spring_qualid_download(self._h, k, buf.ctypes.data, ln.ctypes.data, off.ctypes.data))
+        chk(self._L.spring_qualid_download(self._h, k, buf.ctypes.data, ln.ctypes.data, off.ctypes.data))
         return buf[:n].tobytes(), ln[:self.info["num_units"]], off
 
     def blocks(self, kind):

@@ -14,10 +14,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-
-
-class ReorderError(RuntimeError):
-    """Raised where the reference throws std::runtime_error (call_template_functions.cpp:60)."""
+from ._stage import ReorderError, chk as _chk  # noqa: F401  (both are imported from here elsewhere)
 
 
 @dataclass
@@ -88,11 +85,6 @@ class ReorderOpts:
             o.devices[i] = d
         o.mg_host_transport = int(self.mg_host_transport)
         return o
-
-
-def _chk(rc):
-    if rc != 0:
-        raise ReorderError("%s (code %d)" % (_lib.lib().spring_reorder_last_error().decode(), rc))
 
 
 class ReorderStage:

@@ -7,18 +7,13 @@ import os
 import numpy as np
 
 from . import _lib
-from .reorder import ReorderError
+from ._stage import ReorderError, Stage, chk
 
 # stream ids of include/spring_streams.h -> the file names of reorder_compress_streams.cpp:34-74
 STREAM_FILES = ("read_flag.txt", "read_pos.bin", "read_noise.txt", "read_noisepos.bin", "read_rev.txt",
                 "read_unaligned.txt", "read_lengths.bin", "read_pos_pair.bin", "read_rev_pair.txt")
 STREAM_ID = {f: i for i, f in enumerate(STREAM_FILES)}
 STREAM_ID.update({f.split(".")[0][len("read_"):]: i for i, f in enumerate(STREAM_FILES)})  # "flag", "pos", ...
-
-
-def _chk(rc):
-    if rc != 0:
-        raise ReorderError("%s (code %d)" % (_lib.lib().spring_reorder_last_error().decode(), rc))
 
 
 def _ptr(a):
@@ -30,32 +25,11 @@ def stream_names(paired_end: bool):
     return STREAM_FILES if paired_end else STREAM_FILES[:7]
 
 
-class StreamsStage:
+class StreamsStage(Stage):
     """from_encoder() / from_host(): the encoder's flat streams scattered into the final read order and cut into
     blocks of num_reads_per_block reads (pairs), on the device.  blocks(stream) fetches one stream's blocks."""
 
-    def __init__(self, device: int = -1):
-        self._L = _lib.lib()
-        self._h = C.c_void_p()
-        _chk(self._L.spring_streams_create(device, C.byref(self._h)))
-        self.info = None
-
-    def close(self):
-        if self._h:
-            self._L.spring_streams_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _prefix, _Info = "spring_streams", _lib.StreamsInfo
 
     def from_encoder(self, enc, num_reads, paired_end=False, preserve_order=False, num_reads_per_block=256000,
                      apply_pe_encode=None):
@@ -63,12 +37,8 @@ class StreamsStage:
         pe_encode on a private device copy of the encoder's order; the encoder's own order is left as it was."""
         if apply_pe_encode is None:
             apply_pe_encode = bool(paired_end and not preserve_order)
-        info = _lib.StreamsInfo()
-        self.info = None
-        _chk(self._L.spring_streams_from_encoder(self._h, enc._h, num_reads, int(paired_end), int(preserve_order),
-                                                 num_reads_per_block, int(apply_pe_encode), C.byref(info)))
-        self.info = info.asdict()
-        return self.info
+        return self._run("from_encoder", enc._h, num_reads, int(paired_end), int(preserve_order), num_reads_per_block,
+                         int(apply_pe_encode))
 
     def from_host(self, pos, rc, noise, noisepos, order, rlen, unaligned, num_reads, paired_end=False,
                   preserve_order=False, num_reads_per_block=256000):
@@ -83,24 +53,19 @@ class StreamsStage:
         un = np.frombuffer(bytes(unaligned), np.uint8)
         if order is not None and len(order) != len(rlen):
             raise ReorderError("order and rlen differ in length")
-        info = _lib.StreamsInfo()
-        self.info = None
-        _chk(self._L.spring_streams_from_host(self._h, _ptr(pos), _ptr(rc), len(rc), _ptr(noise), len(noise),
-                                              _ptr(noisepos), len(noisepos), _ptr(order), _ptr(rlen), len(rlen),
-                                              _ptr(un), len(un), num_reads, int(paired_end), int(preserve_order),
-                                              num_reads_per_block, C.byref(info)))
-        self.info = info.asdict()
-        return self.info
+        return self._run("from_host", _ptr(pos), _ptr(rc), len(rc), _ptr(noise), len(noise), _ptr(noisepos),
+                         len(noisepos), _ptr(order), _ptr(rlen), len(rlen), _ptr(un), len(un), num_reads,
+                         int(paired_end), int(preserve_order), num_reads_per_block)
 
     def download(self, stream):
         """-> (bytes of all blocks back to back, block offsets: num_blocks + 1 uint64)."""
         sid = stream if isinstance(stream, int) else STREAM_ID[stream]
         if self.info is None:   # nothing computed (or the last call failed): the library says so
-            _chk(self._L.spring_streams_download(self._h, sid, None, None))
+            chk(self._L.spring_streams_download(self._h, sid, None, None))
         n = self.info["bytes"][sid]
         buf = np.zeros(max(n, 1), np.uint8)
         off = np.zeros(self.info["num_blocks"] + 1, np.uint64)
-        _chk(self._L.spring_streams_download(self._h, sid, buf.ctypes.data, off.ctypes.data))
+        chk(self._L.spring_streams_download(self._h, sid, buf.ctypes.data, off.ctypes.data))
         return buf[:n].tobytes(), off
 
     def blocks(self, stream):
@@ -122,6 +87,6 @@ def call_reorder_compress_streams(temp_dir: str, cp, preserve_order: bool, num_r
     if num_reads is None:
         num_reads = os.path.getsize(os.path.join(temp_dir, "read_lengths.bin")) // 2
     info = _lib.StreamsInfo()
-    _chk(_lib.lib().spring_streams_run(temp_dir.encode(), num_reads, int(cp.paired_end), int(preserve_order),
-                                       num_reads_per_block, device, C.byref(info)))
+    chk(_lib.lib().spring_streams_run(temp_dir.encode(), num_reads, int(cp.paired_end), int(preserve_order),
+                                      num_reads_per_block, device, C.byref(info)))
     return info.asdict()
