@@ -1932,13 +1932,21 @@ static int setup_chains(spring_reorder_ctx *ctx, uint32_t K, uint32_t c0, uint32
 }
 
 // pointers of the double-buffered counters for round t (reorder_device.h): k_round(t) ranks seeds with what
-// k_mg_mark(t-1) counted; k_mg_mark(t) fills the other buffer and zeroes the one just read
-static void set_round_buffers(spring_reorder_ctx *ctx) {
-  DevParams &P = ctx->P;
-  const int w = (int)(ctx->round_no & 1);
-  P.needy_cnt = ctx->cnt_buf[w ^ 1];
-  P.needy_cnt_next = ctx->cnt_buf[w];
+// k_mg_mark(t-1) counted; k_mg_mark(t) fills the other buffer and zeroes the one just read.  (Two groups: each has its own
+// round count and its own DevParams, and the groups touch disjoint blocks of the buffers.)
+static void set_round_buffers(const spring_reorder_ctx *ctx, uint64_t round_no, DevParams &Q) {
+  const int w = (int)(round_no & 1);
+  Q.needy_cnt = ctx->cnt_buf[w ^ 1];
+  Q.needy_cnt_next = ctx->cnt_buf[w];
+}
 
+// shrink deep bins whose tail has been consumed (exact; see k_trim_bins), in both dictionaries.  k_trim_bins moves bin
+// entries, so no search may run beside it: the caller picks the stream and the moment.  `taken`: the bitmap that says which
+// entries are dead (with two chain groups: group 0's view, the smaller one)
+static void trim_deep_bins(const spring_reorder_ctx *ctx, hipStream_t st, const uint64_t *taken) {
+  const DevParams &P = ctx->P;
+  for (int l = 0; l < 2; l++)
+    launch_trim_bins(st, ctx->dict[l].deep, ctx->dict[l].d_ndeep, ctx->dict[l].ndeep, ctx->dict[l].urec, ctx->dict[l].ids, taken, const_cast<ulonglong2 *>(P.sig[l]), P.epos[l]);
 }
 
 // chains still running after the last k_mg_mark: per-wavefront counts summed here (the stream is synchronised)
@@ -1970,10 +1978,85 @@ static DevParams group_params(spring_reorder_ctx *ctx, int g, uint64_t round_no)
     Q.longq = ctx->lb2.longq; Q.lctl = ctx->lb2.lctl; Q.lparts = ctx->lb2.lparts; Q.lhead = ctx->lb2.lhead;
     Q.lbin = ctx->lb2.lbin; Q.lbcode = ctx->lb2.lbcode;
   }
-  const int w = (int)(round_no & 1);  // (set_round_buffers, per group: the groups touch disjoint blocks of the buffers)
-  Q.needy_cnt = ctx->cnt_buf[w ^ 1]; Q.needy_cnt_next = ctx->cnt_buf[w];
+  set_round_buffers(ctx, round_no, Q);
   return Q;
 }
+
+// The host's look at the running chains: the per-wavefront counts the mark steps keep (DevParams::alive_wave), copied
+// behind a batch of rounds into one of two pinned slots; bev[slot] says that the copy is there.
+struct AliveLook {
+  uint32_t *h_aw = nullptr;
+  size_t nw = 0;
+  hipEvent_t bev[2] = {nullptr, nullptr};
+  int init(RunOwned &own, const DevParams &P) {
+    nw = ((size_t)P.Ktot + 63) / 64;
+    HIPCHK(own.pin(&h_aw, 2 * nw * sizeof(uint32_t)));
+    for (auto &e : bev) HIPCHK(own.event(&e, hipEventDisableTiming));
+    return 0;
+  }
+  int queue(hipStream_t st, const DevParams &P, int slot) const {
+    HIPCHK(hipMemcpyAsync(h_aw + (size_t)slot * nw, P.alive_wave, nw * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(bev[slot], st));
+    return 0;
+  }
+};
+
+static uint64_t alive_in(const uint32_t *h_aw, size_t nw, int slot) {
+  uint64_t a = 0;
+  for (size_t i = 0; i < nw; i++) a += h_aw[(size_t)slot * nw + i];
+  return a;
+}
+
+// The time during which at least one of the spans {start, end} ran: the length of their union (sorts them).  Two groups'
+// round kernels run side by side, so the sum of their durations counts most of a batch twice.
+static double union_ms(std::vector<std::pair<float, float>> &iv) {
+  if (iv.empty()) return 0;
+  std::sort(iv.begin(), iv.end());
+  double busy = 0;
+  float cs = iv[0].first, ce = iv[0].second;
+  for (size_t i = 1; i < iv.size(); i++) {
+    if (iv[i].first > ce) { busy += ce - cs; cs = iv[i].first; ce = iv[i].second; }
+    else ce = std::max(ce, iv[i].second);
+  }
+  return busy + (ce - cs);
+}
+
+// The round loop of the chain phase, for every schedule that counts the running chains through an AliveLook.
+// enqueue_batch() queues R rounds (and adds R to `rounds`), count_batch(slot) queues the look behind them into `slot`.
+//   late:  the host looks at the chains still running one batch LATE: batch b + 1 is in the queue before the count of batch b
+//          is waited for, so the GPU never drains while the host synchronises and launches (a bubble of some tens of
+//          microseconds every R rounds).  The price: up to 2 R - 1 rounds over finished chains at the end instead of R - 1
+//          (a round in which every chain is done changes nothing and costs its launches).
+//   !late: a batch at a time, for a driver that reads something back between batches -- after_batch(), called once the
+//          look's copy is there: the other streams' synchronisation, the events of opts.time_search.
+// Returns once a look has seen no running chain.
+extern "C++" {
+template <class Enqueue, class Count, class After>
+static int run_round_loop(const spring_reorder_ctx *ctx, const AliveLook &look, const uint64_t &rounds, bool late, const char *suffix,
+                          Enqueue enqueue_batch, Count count_batch, After after_batch) {
+  uint64_t a = 0;
+  auto running = [&](int slot, uint64_t at) -> int {  // what the look in `slot` saw, taken after `at` rounds
+    HIPCHK(hipEventSynchronize(look.bev[slot]));
+    a = alive_in(look.h_aw, look.nw, slot);
+    HIPCHK(hipGetLastError());
+    if (ctx->o.debug) fprintf(stderr, "[chains] rounds %llu running %llu%s\n", (unsigned long long)at, (unsigned long long)a, suffix);
+    return 0;
+  };
+  int rr;
+  if (!late) {
+    do {
+      if ((rr = enqueue_batch()) || (rr = count_batch(0)) || (rr = running(0, rounds)) || (rr = after_batch())) return rr;
+    } while (a);
+    return 0;
+  }
+  if ((rr = enqueue_batch()) || (rr = count_batch(0))) return rr;
+  for (int b = 0;; b ^= 1) {
+    const uint64_t at = rounds;
+    if ((rr = enqueue_batch()) || (rr = count_batch(b ^ 1)) || (rr = running(b, at))) return rr;
+    if (!a) return 0;
+  }
+}
+}  // extern "C++"
 
 // The two-group schedule (DevParams::phases = 2).  Group 0 runs on the context's stream, group 1 on
 // a second one; a round of a group = its round kernel, then its mark step, which waits (event) for the other group's
@@ -1982,42 +2065,30 @@ static DevParams group_params(spring_reorder_ctx *ctx, int g, uint64_t round_no)
 // for the host.
 static int run_chains_phased(spring_reorder_ctx *ctx, int R, bool timed) {
   DevParams &P = ctx->P;
-  const uint32_t K = P.K;
   const bool stats = ctx->o.collect_stats != 0;
   if (!ctx->st2) HIPCHK(hipStreamCreateWithFlags(&ctx->st2, hipStreamNonBlocking));
   if (!ctx->st3) HIPCHK(hipStreamCreateWithFlags(&ctx->st3, hipStreamNonBlocking));
   hipStream_t sg[2] = {ctx->st, ctx->st2}, sc = ctx->st3;
-  struct Group { uint64_t *taken; uint64_t round_no; } gp[2] = {{P.taken, 0}, {ctx->taken2, 0}};
-  auto params_of = [&](int g) { return group_params(ctx, g, gp[g].round_no); };
+  uint64_t round_no[2] = {0, 0};
+  // an error half way leaves work queued on all three streams: nothing of the run may be in flight when the events and the
+  // pinned buffer go (the guard is destroyed before their owner)
+  RunOwned own;
+  SyncOnError sync_guard{{ctx->st2, ctx->st3, ctx->st}};
   // ev[], ev0, evt only order device work between streams: no system-scope fence (ORDER_ONLY).  What the host reads --
   // alive_wave, copied out once a batch -- waits on cev[], recorded behind the batch's last mark steps with the fence.
   constexpr unsigned ORDER_ONLY = hipEventDisableTiming | hipEventDisableSystemFence;
-  hipEvent_t ev[2] = {nullptr, nullptr}, cev[2] = {nullptr, nullptr}, bev[2] = {nullptr, nullptr}, ev0 = nullptr, evt = nullptr;
-  struct EvFree { hipEvent_t *e; int n; ~EvFree() { for (int i = 0; i < n; i++) if (e[i]) (void)hipEventDestroy(e[i]); } };
-  EvFree g1{ev, 2}, g2{bev, 2}, g3{&ev0, 1}, g4{&evt, 1}, g5{cev, 2};
+  hipEvent_t ev[2], cev[2], ev0, evt;
   for (int i = 0; i < 2; i++) {
-    HIPCHK(hipEventCreateWithFlags(&ev[i], ORDER_ONLY));
-    HIPCHK(hipEventCreateWithFlags(&cev[i], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&bev[i], hipEventDisableTiming));
+    HIPCHK(own.event(&ev[i], ORDER_ONLY));
+    HIPCHK(own.event(&cev[i], hipEventDisableTiming));
   }
-  HIPCHK(hipEventCreateWithFlags(&ev0, ORDER_ONLY));
-  HIPCHK(hipEventCreateWithFlags(&evt, ORDER_ONLY));
-  std::vector<hipEvent_t> tev;  // opts.time_search: an event pair around every round-kernel launch, on the launch's stream
-  struct TevFree { std::vector<hipEvent_t> &v; ~TevFree() { for (auto &e : v) (void)hipEventDestroy(e); } } tev_guard{tev};
-  if (timed) {
-    tev.resize(4 * (size_t)R);
-    for (auto &e : tev) HIPCHK(hipEventCreate(&e));
-  }
-  const size_t nw = ((size_t)K + 63) / 64;
-  uint32_t *h_aw = nullptr;
-  HIPCHK(hipHostMalloc((void **)&h_aw, 2 * nw * sizeof(uint32_t), hipHostMallocDefault));
-  struct HostFree { void *p; ~HostFree() { if (p) (void)hipHostFree(p); } } h_aw_guard{h_aw};
-  // an error half way leaves work queued on all three streams: nothing of the run may be in flight when the events and the
-  // pinned buffer above go (this guard is destroyed before them)
-  struct SyncOnError {
-    spring_reorder_ctx *c; bool ok;
-    ~SyncOnError() { if (!ok) { (void)hipStreamSynchronize(c->st2); (void)hipStreamSynchronize(c->st3); (void)hipStreamSynchronize(c->st); } }
-  } sync_guard{ctx, false};
+  HIPCHK(own.event(&ev0, ORDER_ONLY));
+  HIPCHK(own.event(&evt, ORDER_ONLY));
+  std::vector<hipEvent_t> tev(timed ? 4 * (size_t)R : 0);  // opts.time_search: an event pair around every round-kernel launch, on the launch's stream
+  for (auto &e : tev) HIPCHK(own.event(&e));
+  AliveLook look;
+  int rr = look.init(own, P);
+  if (rr) return rr;
   // group 1 starts behind the set-up (on the context's stream) and half a round late
   HIPCHK(hipEventRecord(ev0, sg[0]));
   HIPCHK(hipStreamWaitEvent(sg[1], ev0, 0));
@@ -2028,25 +2099,24 @@ static int run_chains_phased(spring_reorder_ctx *ctx, int R, bool timed) {
   auto enqueue_batch = [&]() -> int {
     for (int r = 0; r < R; r++) {
       for (int g = 0; g < 2; g++) {
-        const DevParams Q = params_of(g);
+        const DevParams Q = group_params(ctx, g, round_no[g]);
         if (timed) HIPCHK(hipEventRecord(tev[4 * r + 2 * g], sg[g]));
         launch_round(sg[g], Q, stats, false);
         if (timed) HIPCHK(hipEventRecord(tev[4 * r + 2 * g + 1], sg[g]));
         if (g == 1 || have_b) HIPCHK(hipStreamWaitEvent(sg[g], ev[g ^ 1], 0));  // the other group's last mark step
         launch_ph_mark(sg[g], Q);
         HIPCHK(hipEventRecord(ev[g], sg[g]));
-        gp[g].round_no++;
+        round_no[g]++;
       }
       have_b = true;
     }
     for (int g = 0; g < 2; g++) HIPCHK(hipEventRecord(cev[g], sg[g]));
     rounds += R;
     if (P.deep_bins && (ctx->dict[0].ndeep || ctx->dict[1].ndeep)) {
-      // compaction of the deep bins (k_trim_bins moves bin entries: no search may run beside it): both groups meet here, every
-      // R rounds -- the entries it drops are dead in both groups' views (their flags, or group 0's bitmap, the smaller one here)
+      // compaction of the deep bins: both groups meet here, every R rounds -- the entries it drops are dead in both groups'
+      // views (their flags, or group 0's bitmap, the smaller one here)
       HIPCHK(hipStreamWaitEvent(sg[0], ev[1], 0));
-      for (int l = 0; l < 2; l++)
-        launch_trim_bins(sg[0], ctx->dict[l].deep, ctx->dict[l].d_ndeep, ctx->dict[l].ndeep, ctx->dict[l].urec, ctx->dict[l].ids, gp[0].taken, const_cast<ulonglong2 *>(P.sig[l]), P.epos[l]);
+      trim_deep_bins(ctx, sg[0], P.taken);
       HIPCHK(hipEventRecord(evt, sg[0]));
       HIPCHK(hipStreamWaitEvent(sg[1], evt, 0));
     }
@@ -2055,14 +2125,13 @@ static int run_chains_phased(spring_reorder_ctx *ctx, int R, bool timed) {
   auto count_batch = [&](int slot) -> int {  // behind both groups' last mark steps of the batch
     HIPCHK(hipStreamWaitEvent(sc, cev[0], 0));
     HIPCHK(hipStreamWaitEvent(sc, cev[1], 0));
-    HIPCHK(hipMemcpyAsync(h_aw + (size_t)slot * nw, P.alive_wave, nw * 4, hipMemcpyDeviceToHost, sc));
-    HIPCHK(hipEventRecord(bev[slot], sc));
-    return 0;
+    return look.queue(sc, P, slot);
   };
   double ms_busy = 0;
-  auto collect_times = [&]() -> int {  // (time_search: the batch is complete)
-    // summed launch durations, and the time during which at least one of the launches was running: their union (the two
-    // groups' kernels run side by side, so the sum counts most of the batch twice)
+  auto collect_times = [&]() -> int {  // (time_search, a batch at a time: the batch is complete, the events are read)
+    HIPCHK(hipStreamSynchronize(sg[0]));
+    HIPCHK(hipStreamSynchronize(sg[1]));
+    // summed launch durations, and the time during which at least one of the launches was running
     std::vector<std::pair<float, float>> iv(2 * (size_t)R);
     for (int i = 0; i < 2 * R; i++) {
       float ms = 0, s0 = 0;
@@ -2071,50 +2140,18 @@ static int run_chains_phased(spring_reorder_ctx *ctx, int R, bool timed) {
       ms_search += ms;
       iv[i] = {s0, s0 + ms};
     }
-    std::sort(iv.begin(), iv.end());
-    float cs = iv[0].first, ce = iv[0].second;
-    for (size_t i = 1; i < iv.size(); i++) {
-      if (iv[i].first > ce) { ms_busy += ce - cs; cs = iv[i].first; ce = iv[i].second; }
-      else ce = std::max(ce, iv[i].second);
-    }
-    ms_busy += ce - cs;
+    ms_busy += union_ms(iv);
     launches += 2 * (uint64_t)R;
     return 0;
   };
-  int rr;
-  if (timed) {  // a batch at a time (the events are read between batches)
-    for (;;) {
-      if ((rr = enqueue_batch())) return rr;
-      if ((rr = count_batch(0))) return rr;
-      HIPCHK(hipEventSynchronize(bev[0]));
-      HIPCHK(hipStreamSynchronize(sg[0]));
-      HIPCHK(hipStreamSynchronize(sg[1]));
-      if ((rr = collect_times())) return rr;
-      uint64_t a = 0;
-      for (size_t i = 0; i < nw; i++) a += h_aw[i];
-      if (!a) break;
-    }
-  } else {
-    if ((rr = enqueue_batch())) return rr;
-    if ((rr = count_batch(0))) return rr;
-    for (int b = 0;; b ^= 1) {
-      if ((rr = enqueue_batch())) return rr;
-      if ((rr = count_batch(b ^ 1))) return rr;
-      HIPCHK(hipEventSynchronize(bev[b]));
-      uint64_t a = 0;
-      for (size_t i = 0; i < nw; i++) a += h_aw[(size_t)b * nw + i];
-      HIPCHK(hipGetLastError());
-      if (ctx->o.debug) fprintf(stderr, "[chains] rounds %llu running %llu (two groups)\n", (unsigned long long)(rounds - R), (unsigned long long)a);
-      if (!a) break;
-    }
-  }
+  if ((rr = run_round_loop(ctx, look, rounds, !timed, " (two groups)", enqueue_batch, count_batch, collect_times))) return rr;
   // everything behind the chain phase is queued on the context's stream
   HIPCHK(hipStreamWaitEvent(sg[0], ev[1], 0));
   HIPCHK(hipEventRecord(ctx->ev[5], sg[0]));
   HIPCHK(hipStreamSynchronize(sg[1]));
   HIPCHK(hipStreamSynchronize(sc));
   HIPCHK(hipStreamSynchronize(sg[0]));
-  ctx->round_no = gp[0].round_no;
+  ctx->round_no = round_no[0];
   ctx->stats.rounds = rounds;
   ctx->stats.ms_search_kernel = ms_search;
   ctx->stats.ms_search_busy = ms_busy;
@@ -2156,15 +2193,13 @@ int spring_reorder_run_chains(spring_reorder_ctx *ctx) {
     ctx->stage = ST_CHAINS;
     return 0;
   }
-  std::vector<hipEvent_t> tev;
-  if (timed) {
-    tev.resize(2 * (size_t)R);
-    for (auto &e : tev) HIPCHK(hipEventCreate(&e));
-  }
+  RunOwned own;
+  SyncOnError sync_guard{{st}};  // (every early return below: nothing of the run is in flight when `own` lets go)
+  std::vector<hipEvent_t> tev(timed ? 2 * (size_t)R : 0);
+  for (auto &e : tev) HIPCHK(own.event(&e));
   uint32_t *h_alive = nullptr;
   std::vector<uint32_t> alive_tmp;
-  HIPCHK(hipHostMalloc((void **)&h_alive, sizeof(uint32_t), hipHostMallocDefault));
-  struct HostFree { void *p; ~HostFree() { if (p) (void)hipHostFree(p); } } h_alive_guard{h_alive};  // (every early return below)
+  HIPCHK(own.pin(&h_alive, sizeof(uint32_t)));
   uint64_t rounds = 0;
   double ms_search = 0;
   uint64_t launches = 0;
@@ -2174,7 +2209,7 @@ int spring_reorder_run_chains(spring_reorder_ctx *ctx) {
     for (int r = 0; r < R; r++) {
       if (timed) HIPCHK(hipEventRecord(tev[2 * r], st));
       if (fused) {
-        set_round_buffers(ctx);
+        set_round_buffers(ctx, ctx->round_no, P);
         launch_round(st, P, stats, false);
         if (timed) HIPCHK(hipEventRecord(tev[2 * r + 1], st));
         launch_mg_mark(st, P);
@@ -2186,42 +2221,19 @@ int spring_reorder_run_chains(spring_reorder_ctx *ctx) {
       }
     }
     rounds += R;
-    for (int l = 0; l < 2; l++)  // shrink deep bins whose tail has been consumed (exact; see k_trim_bins)
-      launch_trim_bins(st, ctx->dict[l].deep, ctx->dict[l].d_ndeep, ctx->dict[l].ndeep, ctx->dict[l].urec, ctx->dict[l].ids, P.taken, const_cast<ulonglong2 *>(P.sig[l]), P.epos[l]);
+    trim_deep_bins(ctx, st, P.taken);
     return 0;
   };
-  if (fused && !timed && *h_alive) {
-    // The host looks at the chains still running one batch LATE: batch b + 1 is in the queue before the count of batch b is
-    // waited for, so the GPU never drains while the host synchronises and launches (a bubble of some tens of microseconds
-    // every R rounds).  The price: up to 2 R - 1 rounds over finished chains at the end instead of R - 1 (a round in which
-    // every chain is done changes nothing and costs its launches).
-    const size_t nw = ((size_t)P.Ktot + 63) / 64;
-    uint32_t *h_aw = nullptr;
-    HIPCHK(hipHostMalloc((void **)&h_aw, 2 * nw * sizeof(uint32_t), hipHostMallocDefault));
-    HostFree h_aw_guard{h_aw};
-    hipEvent_t bev[2] = {nullptr, nullptr};
-    struct EvFree { hipEvent_t *e; ~EvFree() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } bev_guard{bev};
-    for (int i = 0; i < 2; i++) HIPCHK(hipEventCreateWithFlags(&bev[i], hipEventDisableTiming));
-    auto count_batch = [&](int slot) -> int {  // (queued behind the batch: the per-64-chain counts k_mg_mark keeps)
-      HIPCHK(hipMemcpyAsync(h_aw + (size_t)slot * nw, P.alive_wave, nw * 4, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipEventRecord(bev[slot], st));
-      return 0;
-    };
-    int rr;
-    if ((rr = enqueue_batch())) return rr;
-    if ((rr = count_batch(0))) return rr;
-    for (int b = 0;; b ^= 1) {
-      if ((rr = enqueue_batch())) return rr;
-      if ((rr = count_batch(b ^ 1))) return rr;
-      HIPCHK(hipEventSynchronize(bev[b]));
-      uint64_t a = 0;
-      for (size_t i = 0; i < nw; i++) a += h_aw[(size_t)b * nw + i];
-      HIPCHK(hipGetLastError());
-      if (ctx->o.debug) fprintf(stderr, "[chains] rounds %llu running %llu\n", (unsigned long long)(rounds - R), (unsigned long long)a);
-      if (!a) break;
-    }
+  if (fused && !timed && *h_alive) {  // the host looks one batch late (run_round_loop), at the per-64-chain counts k_mg_mark keeps
+    AliveLook look;
+    int rr = look.init(own, P);
+    if (rr) return rr;
+    rr = run_round_loop(ctx, look, rounds, true, "", enqueue_batch, [&](int slot) { return look.queue(st, P, slot); }, [] { return 0; });
+    if (rr) return rr;
     *h_alive = 0;
   }
+  // every other one-group schedule counts on the context's stream with nothing else in the queue, so it needs neither slots
+  // nor events: a plain loop, a batch at a time
   while (*h_alive) {
     int rr = enqueue_batch();
     if (rr) return rr;
@@ -2246,7 +2258,7 @@ int spring_reorder_run_chains(spring_reorder_ctx *ctx) {
   }
   HIPCHK(hipEventRecord(ctx->ev[5], st));
   HIPCHK(hipStreamSynchronize(st));
-  for (auto &e : tev) (void)hipEventDestroy(e);
+  sync_guard.ok = true;
   ctx->stats.rounds = rounds;
   ctx->stats.ms_search_kernel = ms_search;
   ctx->stats.ms_search_busy = ms_search;
@@ -2290,7 +2302,7 @@ int spring_reorder_mg_search(spring_reorder_ctx *ctx) {
     // last mark step only)
     for (int g = 0; g < 2; g++) launch_round(ctx->st, group_params(ctx, g, ctx->round_no), ctx->o.collect_stats != 0, true);
   } else {
-    set_round_buffers(ctx);
+    set_round_buffers(ctx, ctx->round_no, ctx->P);
     launch_round(ctx->st, ctx->P, ctx->o.collect_stats != 0, true);
   }
   HIPCHK(hipGetLastError());
@@ -2342,9 +2354,7 @@ int spring_reorder_mg_apply(spring_reorder_ctx *ctx, int32_t check_alive, uint32
   HIPCHK(hipGetLastError());
   ctx->round_no++;
   ctx->stats.rounds++;
-  if (ctx->stats.rounds % 16 == 0)
-    for (int l = 0; l < 2; l++)
-      launch_trim_bins(st, ctx->dict[l].deep, ctx->dict[l].d_ndeep, ctx->dict[l].ndeep, ctx->dict[l].urec, ctx->dict[l].ids, ctx->P.taken, const_cast<ulonglong2 *>(ctx->P.sig[l]), ctx->P.epos[l]);
+  if (ctx->stats.rounds % 16 == 0) trim_deep_bins(ctx, st, ctx->P.taken);
   if (check_alive) {
     uint32_t a = 0;
     std::vector<uint32_t> tmp;
@@ -2497,30 +2507,25 @@ static int mg_run_phased(spring_reorder_ctx *ctx, spring_mg_comm *comm) {
   if (!ctx->st2) HIPCHK(hipStreamCreateWithFlags(&ctx->st2, hipStreamNonBlocking));
   if (!ctx->st3) HIPCHK(hipStreamCreateWithFlags(&ctx->st3, hipStreamNonBlocking));
   hipStream_t sg[2] = {ctx->st, ctx->st2}, sx = ctx->st3;
-  hipEvent_t ev[2] = {nullptr, nullptr}, ek[2] = {nullptr, nullptr}, ex[2] = {nullptr, nullptr}, bev[2] = {nullptr, nullptr}, ev0 = nullptr;
-  struct EvFree { hipEvent_t *e; int n; ~EvFree() { for (int i = 0; i < n; i++) if (e[i]) (void)hipEventDestroy(e[i]); } };
-  EvFree f1{ev, 2}, f2{ek, 2}, f3{ex, 2}, f4{bev, 2}, f5{&ev0, 1};
+  // (an error half way: nothing of this run may still be queued on the three streams when the events and the pinned buffers
+  // go, nor when the caller hands the context's buffers back)
+  RunOwned own;
+  SyncOnError sync_guard{{ctx->st, ctx->st2, ctx->st3}};
+  hipEvent_t ev[2], ek[2], ex[2], ev0;
   for (int i = 0; i < 2; i++) {
-    HIPCHK(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ek[i], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ex[i], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&bev[i], hipEventDisableTiming));
+    HIPCHK(own.event(&ev[i], hipEventDisableTiming));
+    HIPCHK(own.event(&ek[i], hipEventDisableTiming));
+    HIPCHK(own.event(&ex[i], hipEventDisableTiming));
   }
-  HIPCHK(hipEventCreateWithFlags(&ev0, hipEventDisableTiming));
-  std::vector<hipEvent_t> tev;  // time_search: per round and group {round kernel start, end, exchange end (on sx), mark end}
-  struct TevFree { std::vector<hipEvent_t> &v; ~TevFree() { for (auto &e : v) if (e) (void)hipEventDestroy(e); } } tev_guard{tev};
-  if (timed) {
-    tev.assign(8 * (size_t)R, nullptr);
-    for (auto &e : tev) HIPCHK(hipEventCreate(&e));
-  }
-  const size_t nw = ((size_t)P.Ktot + 63) / 64;
-  uint32_t *h_aw = nullptr;
-  HIPCHK(hipHostMalloc((void **)&h_aw, 2 * nw * sizeof(uint32_t), hipHostMallocDefault));
-  struct HostFree { void *p; ~HostFree() { if (p) (void)hipHostFree(p); } } h_aw_guard{h_aw};
-  void *h_stage = nullptr;  // host transport: one staging buffer per group's range
+  HIPCHK(own.event(&ev0, hipEventDisableTiming));
+  std::vector<hipEvent_t> tev(timed ? 8 * (size_t)R : 0);  // time_search: per round and group {round kernel start, end, exchange end (on sx), mark end}
+  for (auto &e : tev) HIPCHK(own.event(&e));
+  AliveLook look;
+  int rr = look.init(own, P);
+  if (rr) return rr;
+  char *h_stage = nullptr;  // host transport: one staging buffer per group's range
   const size_t gbytes[2] = {(size_t)ctx->grp[0].gKg * 8, (size_t)ctx->grp[1].gKg * 8};
-  if (comm->host_fn) HIPCHK(hipHostMalloc(&h_stage, std::max(gbytes[0], gbytes[1]), hipHostMallocDefault));
-  HostFree h_stage_guard{h_stage};
+  if (comm->host_fn) HIPCHK(own.pin(&h_stage, std::max(gbytes[0], gbytes[1])));
   uint64_t round_no[2] = {0, 0};
   HIPCHK(hipEventRecord(ev0, sg[0]));
   HIPCHK(hipStreamWaitEvent(sg[1], ev0, 0));
@@ -2528,10 +2533,6 @@ static int mg_run_phased(spring_reorder_ctx *ctx, spring_mg_comm *comm) {
   bool have_b = false;
   uint64_t rounds = 0, timed_rounds = 0;
   double ms_round = 0, ms_xchg = 0, ms_mark = 0, ms_busy = 0;
-  auto fail_sync = [&](int code) {  // (nothing of this run may still be queued when the caller tears the context down)
-    (void)hipStreamSynchronize(sg[0]); (void)hipStreamSynchronize(sg[1]); (void)hipStreamSynchronize(sx);
-    return code;
-  };
   auto enqueue_batch = [&]() -> int {
     for (int r = 0; r < R; r++) {
       for (int g = 0; g < 2; g++) {
@@ -2552,7 +2553,7 @@ static int mg_run_phased(spring_reorder_ctx *ctx, spring_mg_comm *comm) {
           HIPCHK(hipStreamWaitEvent(sg[g], ex[g], 0));
         } else {  // through the caller's all-gather on host memory (ranks that share a device; tests): synchronous
           const size_t off = (size_t)(a.c0 + a.g0 - a.gg0) * 8, slice = (size_t)a.Kg * 8;
-          HIPCHK(hipMemcpyAsync((char *)h_stage + off, mine, slice, hipMemcpyDeviceToHost, sg[g]));
+          HIPCHK(hipMemcpyAsync(h_stage + off, mine, slice, hipMemcpyDeviceToHost, sg[g]));
           HIPCHK(hipStreamSynchronize(sg[g]));
           if (comm->host_fn(h_stage, off, slice, gbytes[g], comm->host_user))
             return fail(SPRING_REORDER_E_IO, "mg_run: the caller's all-gather reported an error");
@@ -2572,8 +2573,7 @@ static int mg_run_phased(spring_reorder_ctx *ctx, spring_mg_comm *comm) {
     rounds += R;
     if (P.deep_bins && (ctx->dict[0].ndeep || ctx->dict[1].ndeep)) {  // (as in run_chains_phased: both groups meet)
       HIPCHK(hipStreamWaitEvent(sg[0], ev[1], 0));
-      for (int l = 0; l < 2; l++)
-        launch_trim_bins(sg[0], ctx->dict[l].deep, ctx->dict[l].d_ndeep, ctx->dict[l].ndeep, ctx->dict[l].urec, ctx->dict[l].ids, P.taken, const_cast<ulonglong2 *>(P.sig[l]), P.epos[l]);
+      trim_deep_bins(ctx, sg[0], P.taken);
       HIPCHK(hipEventRecord(ev0, sg[0]));
       HIPCHK(hipStreamWaitEvent(sg[1], ev0, 0));
     }
@@ -2584,57 +2584,32 @@ static int mg_run_phased(spring_reorder_ctx *ctx, spring_mg_comm *comm) {
   auto count_batch = [&](int slot) -> int {
     HIPCHK(hipStreamWaitEvent(sx, ev[0], 0));
     HIPCHK(hipStreamWaitEvent(sx, ev[1], 0));
-    HIPCHK(hipMemcpyAsync(h_aw + (size_t)slot * nw, P.alive_wave, nw * 4, hipMemcpyDeviceToHost, sx));
-    HIPCHK(hipEventRecord(bev[slot], sx));
+    return look.queue(sx, P, slot);
+  };
+  auto after_batch = [&]() -> int {  // (a batch at a time: the batch is complete)
+    HIPCHK(hipStreamSynchronize(sg[0]));
+    HIPCHK(hipStreamSynchronize(sg[1]));
+    if (!timed) return 0;
+    // per group-round: round kernel | all-gather (from the end of the round kernel to the end of the collective on the exchange
+    // stream) | resolve + mark (incl. the wait for the other group's mark step); and the union of the round kernels'
+    // intervals: the time during which at least one round kernel ran -- the rank's critical path if everything else hides
+    std::vector<std::pair<float, float>> iv(2 * (size_t)R);
+    for (int i = 0; i < 2 * R; i++) {
+      float a = 0, b = 0, c = 0, s0 = 0;
+      HIPCHK(hipEventElapsedTime(&a, tev[4 * i], tev[4 * i + 1]));
+      HIPCHK(hipEventElapsedTime(&b, tev[4 * i + 1], tev[4 * i + 2]));
+      HIPCHK(hipEventElapsedTime(&c, tev[4 * i + 2], tev[4 * i + 3]));
+      HIPCHK(hipEventElapsedTime(&s0, tev[0], tev[4 * i]));
+      ms_round += a; ms_xchg += b; ms_mark += c;
+      iv[(size_t)i] = {s0, s0 + a};
+    }
+    ms_busy += union_ms(iv);
+    timed_rounds += (uint64_t)R;
     return 0;
   };
-  auto alive_in = [&](int slot) { uint64_t a = 0; for (size_t i = 0; i < nw; i++) a += h_aw[(size_t)slot * nw + i]; return a; };
-  int rr = 0;
-  if (timed || comm->host_fn) {  // a batch at a time
-    for (;;) {
-      if ((rr = enqueue_batch())) return fail_sync(rr);
-      if ((rr = count_batch(0))) return fail_sync(rr);
-      HIPCHK(hipEventSynchronize(bev[0]));
-      HIPCHK(hipStreamSynchronize(sg[0]));
-      HIPCHK(hipStreamSynchronize(sg[1]));
-      if (timed) {
-        // per group-round: round kernel | all-gather (from the end of the round kernel to the end of the collective on the exchange
-        // stream) | resolve + mark (incl. the wait for the other group's mark step); and the union of the round kernels'
-        // intervals: the time during which at least one round kernel ran -- the rank's critical path if everything else hides
-        std::vector<std::pair<float, float>> iv(2 * (size_t)R);
-        for (int i = 0; i < 2 * R; i++) {
-          float a = 0, b = 0, c = 0, s0 = 0;
-          (void)hipEventElapsedTime(&a, tev[4 * i], tev[4 * i + 1]);
-          (void)hipEventElapsedTime(&b, tev[4 * i + 1], tev[4 * i + 2]);
-          (void)hipEventElapsedTime(&c, tev[4 * i + 2], tev[4 * i + 3]);
-          (void)hipEventElapsedTime(&s0, tev[0], tev[4 * i]);
-          ms_round += a; ms_xchg += b; ms_mark += c;
-          iv[(size_t)i] = {s0, s0 + a};
-        }
-        std::sort(iv.begin(), iv.end());
-        float cs = iv[0].first, ce = iv[0].second;
-        for (size_t i = 1; i < iv.size(); i++) {
-          if (iv[i].first > ce) { ms_busy += ce - cs; cs = iv[i].first; ce = iv[i].second; }
-          else ce = std::max(ce, iv[i].second);
-        }
-        ms_busy += ce - cs;
-        timed_rounds += (uint64_t)R;
-      }
-      if (!alive_in(0)) break;
-    }
-  } else {  // the host looks at the count one batch late: neither group's stream ever waits for it
-    if ((rr = enqueue_batch())) return fail_sync(rr);
-    if ((rr = count_batch(0))) return fail_sync(rr);
-    for (int b = 0;; b ^= 1) {
-      if ((rr = enqueue_batch())) return fail_sync(rr);
-      if ((rr = count_batch(b ^ 1))) return fail_sync(rr);
-      HIPCHK(hipEventSynchronize(bev[b]));
-      const uint64_t a = alive_in(b);
-      HIPCHK(hipGetLastError());
-      if (ctx->o.debug) fprintf(stderr, "[chains] rounds %llu running %llu (pool, two groups)\n", (unsigned long long)(rounds - R), (unsigned long long)a);
-      if (!a) break;
-    }
-  }
+  // untimed over RCCL the host looks at the count one batch late: neither group's stream ever waits for it
+  const bool late = !(timed || comm->host_fn);
+  if ((rr = run_round_loop(ctx, look, rounds, late, " (pool, two groups)", enqueue_batch, count_batch, after_batch))) return rr;
   HIPCHK(hipStreamWaitEvent(sg[0], ev[1], 0));
   HIPCHK(hipStreamSynchronize(sg[1]));
   HIPCHK(hipStreamSynchronize(sx));
@@ -2645,6 +2620,75 @@ static int mg_run_phased(spring_reorder_ctx *ctx, spring_mg_comm *comm) {
     ctx->stats.ms_search_kernel = ms_round; ctx->stats.ms_search_busy = ms_busy; ctx->stats.search_launches = 2 * timed_rounds;
     ctx->stats.ms_exchange = ms_xchg; ctx->stats.ms_resolve_mark = ms_mark;
   }
+  sync_guard.ok = true;
+  return 0;
+}
+
+// The pool with one chain group: round kernel -> exchange -> resolve + mark, all on the context's stream; the running chains are
+// recounted on that stream after every batch (running_chains), so this is a plain loop, a batch at a time.
+static int mg_run_one_group(spring_reorder_ctx *ctx, spring_mg_comm *comm) {
+  hipStream_t st = ctx->st;
+  DevParams &P = ctx->P;
+  const bool stats = ctx->o.collect_stats != 0;
+  const int R = ctx->o.rounds_per_sync > 0 ? ctx->o.rounds_per_sync : 8;
+  const size_t slice = (size_t)P.K * 8, total = (size_t)P.Ktot * 8;
+  RunOwned own;
+  SyncOnError sync_guard{{st}};
+  char *h_stage = nullptr;  // host transport: the staging buffer of the exchange
+  if (comm->host_fn) HIPCHK(own.pin(&h_stage, total));
+  // time_search: four events per round (round kernel | exchange | resolve + mark), read back at every host check
+  const bool timed = ctx->o.time_search != 0;
+  std::vector<hipEvent_t> tev(timed ? 4 * (size_t)R : 0);
+  for (auto &e : tev) HIPCHK(own.event(&e));
+  double ms_round = 0, ms_xchg = 0, ms_mark = 0;
+  uint64_t timed_rounds = 0;
+  uint32_t alive = 1;
+  std::vector<uint32_t> alive_tmp;
+  while (alive) {
+    for (int i = 0; i < R; i++) {
+      set_round_buffers(ctx, ctx->round_no, P);
+      if (timed) HIPCHK(hipEventRecord(tev[4 * i], st));
+      launch_round(st, P, stats, true);
+      if (timed) HIPCHK(hipEventRecord(tev[4 * i + 1], st));
+      if (comm->rccl) {  // in place: this rank's words already sit at their offset of the receive buffer
+        const int e = g_rccl.AllGather(P.prop + P.c0, P.prop, P.K, RCCL_UINT64, comm->rccl, st);
+        if (e) return fail(SPRING_REORDER_E_HIP, "ncclAllGather: %s", rccl_err(e));
+      } else {
+        HIPCHK(hipMemcpyAsync(h_stage + (size_t)P.c0 * 8, P.prop + P.c0, slice, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (comm->host_fn(h_stage, (size_t)P.c0 * 8, slice, total, comm->host_user))
+          return fail(SPRING_REORDER_E_IO, "mg_run: the caller's all-gather reported an error");
+        HIPCHK(hipMemcpyAsync(P.prop, h_stage, total, hipMemcpyHostToDevice, st));
+      }
+      if (timed) HIPCHK(hipEventRecord(tev[4 * i + 2], st));
+      launch_mg_resolve(st, P);
+      launch_mg_mark(st, P);
+      if (timed) HIPCHK(hipEventRecord(tev[4 * i + 3], st));
+      ctx->round_no++;
+      ctx->stats.rounds++;
+      if (ctx->stats.rounds % 16 == 0) trim_deep_bins(ctx, st, P.taken);
+    }
+    if (timed) {
+      HIPCHK(hipStreamSynchronize(st));
+      for (int i = 0; i < R; i++) {
+        float a = 0, b = 0, c = 0;
+        HIPCHK(hipEventElapsedTime(&a, tev[4 * i], tev[4 * i + 1]));
+        HIPCHK(hipEventElapsedTime(&b, tev[4 * i + 1], tev[4 * i + 2]));
+        HIPCHK(hipEventElapsedTime(&c, tev[4 * i + 2], tev[4 * i + 3]));
+        ms_round += a; ms_xchg += b; ms_mark += c;
+      }
+      timed_rounds += (uint64_t)R;
+    }
+    // every rank recounted the running chains from the same gathered words: the same decision everywhere
+    const int ra = running_chains(ctx, alive_tmp, &alive);
+    if (ra) return ra;
+    HIPCHK(hipGetLastError());
+  }
+  if (timed) {
+    ctx->stats.ms_search_kernel = ms_round; ctx->stats.ms_search_busy = ms_round; ctx->stats.search_launches = timed_rounds;
+    ctx->stats.ms_exchange = ms_xchg; ctx->stats.ms_resolve_mark = ms_mark;
+  }
+  sync_guard.ok = true;  // (mg_end synchronises the stream)
   return 0;
 }
 
@@ -2655,106 +2699,15 @@ int spring_reorder_mg_run(spring_reorder_ctx *ctx, spring_mg_comm *comm, uint32_
     return fail(SPRING_REORDER_E_ARG, "mg_run: the communicator lives on device %d, the context on %d", comm->dev, ctx->dev);
   int r = spring_reorder_mg_begin(ctx, comm->rank, comm->world, total_chains, nullptr);
   if (r) return r;
-  if (ctx->P.phases == 2) {  // two chain groups: a slice of each per rank, the exchanges beside the round kernels
-    const int rp = mg_run_phased(ctx, comm);
-    const std::string keep = g_err;
-    const int re = spring_reorder_mg_end(ctx);
-    if (rp) { g_err = keep; return rp; }
-    return re;
-  }
-  hipStream_t st = ctx->st;
-  DevParams &P = ctx->P;
-  const bool stats = ctx->o.collect_stats != 0;
-  const int R = ctx->o.rounds_per_sync > 0 ? ctx->o.rounds_per_sync : 8;
-  const size_t slice = (size_t)P.K * 8, total = (size_t)P.Ktot * 8;
-  uint32_t *h_alive = nullptr;
-  std::vector<uint32_t> alive_tmp;
-  void *h_stage = nullptr;
-  HIPCHK(hipHostMalloc((void **)&h_alive, sizeof(uint32_t), hipHostMallocDefault));
-  if (comm->host_fn && hipHostMalloc(&h_stage, total, hipHostMallocDefault) != hipSuccess) {
-    (void)hipHostFree(h_alive);
-    (void)spring_reorder_mg_end(ctx);
-    return fail(SPRING_REORDER_E_HIP, "mg_run: cannot pin the exchange staging buffer");
-  }
-  int ret = 0;
-  *h_alive = 1;
-  // time_search: four events per round (round kernel | exchange | resolve + mark), read back at every host check
-  const bool timed = ctx->o.time_search != 0;
-  std::vector<hipEvent_t> tev;
-  if (timed) {
-    tev.resize(4 * (size_t)R);
-    for (auto &e : tev) if (hipEventCreate(&e) != hipSuccess) { ret = fail(SPRING_REORDER_E_HIP, "mg_run: hipEventCreate failed"); break; }
-  }
-  double ms_round = 0, ms_xchg = 0, ms_mark = 0;
-  uint64_t timed_rounds = 0;
-  while (*h_alive && !ret) {
-    int done_rounds = 0;
-    for (int i = 0; i < R && !ret; i++) {
-      set_round_buffers(ctx);
-      if (timed) (void)hipEventRecord(tev[4 * i], st);
-      launch_round(st, P, stats, true);
-      if (timed) (void)hipEventRecord(tev[4 * i + 1], st);
-      if (comm->rccl) {  // in place: this rank's words already sit at their offset of the receive buffer
-        const int e = g_rccl.AllGather(P.prop + P.c0, P.prop, P.K, RCCL_UINT64, comm->rccl, st);
-        if (e) ret = fail(SPRING_REORDER_E_HIP, "ncclAllGather: %s", rccl_err(e));
-      } else {
-        hipError_t he = hipMemcpyAsync((char *)h_stage + (size_t)P.c0 * 8, P.prop + P.c0, slice, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he != hipSuccess) { ret = fail(SPRING_REORDER_E_HIP, "staging copy failed: %s", hipGetErrorString(he)); break; }
-        if (comm->host_fn(h_stage, (size_t)P.c0 * 8, slice, total, comm->host_user)) {
-          ret = fail(SPRING_REORDER_E_IO, "mg_run: the caller's all-gather reported an error");
-          break;
-        }
-        he = hipMemcpyAsync(P.prop, h_stage, total, hipMemcpyHostToDevice, st);
-        if (he != hipSuccess) { ret = fail(SPRING_REORDER_E_HIP, "staging copy failed: %s", hipGetErrorString(he)); break; }
-      }
-      if (timed) (void)hipEventRecord(tev[4 * i + 2], st);
-      launch_mg_resolve(st, P);
-      launch_mg_mark(st, P);
-      if (timed) (void)hipEventRecord(tev[4 * i + 3], st);
-      done_rounds = i + 1;
-      ctx->round_no++;
-      ctx->stats.rounds++;
-      if (ctx->stats.rounds % 16 == 0)
-        for (int l = 0; l < 2; l++)
-          launch_trim_bins(st, ctx->dict[l].deep, ctx->dict[l].d_ndeep, ctx->dict[l].ndeep, ctx->dict[l].urec, ctx->dict[l].ids, P.taken, const_cast<ulonglong2 *>(P.sig[l]), P.epos[l]);
-    }
-    if (ret) break;
-    if (timed) {
-      (void)hipStreamSynchronize(st);
-      for (int i = 0; i < done_rounds; i++) {
-        float a = 0, b = 0, c = 0;
-        (void)hipEventElapsedTime(&a, tev[4 * i], tev[4 * i + 1]);
-        (void)hipEventElapsedTime(&b, tev[4 * i + 1], tev[4 * i + 2]);
-        (void)hipEventElapsedTime(&c, tev[4 * i + 2], tev[4 * i + 3]);
-        ms_round += a; ms_xchg += b; ms_mark += c;
-      }
-      timed_rounds += (uint64_t)done_rounds;
-    }
-    // every rank recounted the running chains from the same gathered words: the same decision everywhere
-    ret = running_chains(ctx, alive_tmp, h_alive);
-    if (!ret) {
-      hipError_t he = hipGetLastError();
-      if (he != hipSuccess) ret = fail(SPRING_REORDER_E_HIP, "mg_run: %s", hipGetErrorString(he));
-    }
-  }
-  (void)hipHostFree(h_alive);
-  if (h_stage) (void)hipHostFree(h_stage);
-  for (auto &e : tev) if (e) (void)hipEventDestroy(e);
-  if (timed) {
-    ctx->stats.ms_search_kernel = ms_round; ctx->stats.ms_search_busy = ms_round; ctx->stats.search_launches = timed_rounds;
-    ctx->stats.ms_exchange = ms_xchg; ctx->stats.ms_resolve_mark = ms_mark;
-  }
-  if (ret) {
-    // a failed rank leaves the pool: its peers are stuck in the exchange until the caller tears the communicator
-    // down (RCCL) or makes its all-gather callback fail (host transport) -- the context itself is left consistent
-    const std::string keep = g_err;
-    (void)hipStreamSynchronize(st);
-    (void)spring_reorder_mg_end(ctx);
-    g_err = keep;
-    return ret;
-  }
-  return spring_reorder_mg_end(ctx);
+  // two chain groups: a slice of each per rank, the exchanges beside the round kernels
+  const int rr = ctx->P.phases == 2 ? mg_run_phased(ctx, comm) : mg_run_one_group(ctx, comm);
+  // The one way out, whatever happened: the driver's guard has drained its streams, the context leaves the pool.  A failed
+  // rank's peers are stuck in the exchange until the caller tears the communicator down (RCCL) or makes its all-gather
+  // callback fail (host transport) -- the context itself is left consistent, and the first error is the one reported.
+  const std::string keep = g_err;
+  const int re = spring_reorder_mg_end(ctx);
+  if (rr) { g_err = keep; return rr; }
+  return re;
 }
 
 int spring_reorder_finalize(spring_reorder_ctx *ctx) {

@@ -9,6 +9,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "reorder_internal.h"
 
 // A macro, so that the file and the line are the caller's.  Needs `fail` in scope (using sr::fail, or namespace sr).
@@ -55,10 +57,43 @@ struct Events {
   ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
 };
 
+// What one run of a driver allocates on the host side: any number of events, each with its own creation flags, and pinned
+// buffers.  All of it goes with the holder.
+struct RunOwned {
+  std::vector<hipEvent_t> events;
+  std::vector<void *> pinned;
+  RunOwned() = default;
+  RunOwned(const RunOwned &) = delete;
+  RunOwned &operator=(const RunOwned &) = delete;
+  ~RunOwned() {
+    for (auto e : events) (void)hipEventDestroy(e);
+    for (auto p : pinned) (void)hipHostFree(p);
+  }
+  hipError_t event(hipEvent_t *e, unsigned flags = hipEventDefault) {
+    const hipError_t r = hipEventCreateWithFlags(e, flags);
+    if (r == hipSuccess) events.push_back(*e);
+    return r;
+  }
+  template <class T> hipError_t pin(T **p, size_t bytes) {
+    const hipError_t r = hipHostMalloc((void **)p, bytes, hipHostMallocDefault);
+    if (r == hipSuccess) pinned.push_back(*p);
+    return r;
+  }
+};
+
 // Declare it behind the buffers of a function: whatever is in flight ends before they go back to the pool.
 struct SyncOnExit {
   hipStream_t st;
   ~SyncOnExit() { (void)hipStreamSynchronize(st); }
+};
+
+// The same for a run over up to three streams that ends with a synchronisation of its own: declare it behind the run's
+// owners and set `ok` in front of the successful return.  On every other exit nothing of the run is in flight any more
+// when the events, the pinned buffers and -- in the caller -- the context's device buffers are released.
+struct SyncOnError {
+  hipStream_t st[3] = {};
+  bool ok = false;
+  ~SyncOnError() { if (!ok) for (auto s : st) if (s) (void)hipStreamSynchronize(s); }
 };
 
 // The device of a new context: *device < 0 picks the current one.  `what` names the stage in the message.
