@@ -13,3 +13,4 @@ from .gzip import GzipStage  # noqa: F401,E402
 from .bwt import BwtStage  # noqa: F401,E402
 from .unbwt import UnbwtStage  # noqa: F401,E402
 from .idcodec import IdCodecStage  # noqa: F401,E402
+from .qlfc import QlfcStage  # noqa: F401,E402

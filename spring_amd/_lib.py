@@ -82,6 +82,16 @@ IDCODEC_EXPORTS = [
     "spring_idcodec_workspace_need", "spring_idcodec_from_qualid", "spring_idcodec_from_host", "spring_idcodec_download",
     "spring_idcodec_symbols", "spring_idcodec_get_info",
 ]
+# include/spring_qlfc.h: a list of its own as well
+QLFC_EXPORTS = [
+    "spring_qlfc_create", "spring_qlfc_destroy", "spring_qlfc_set_state_tables", "spring_qlfc_set_workspace_bytes",
+    "spring_qlfc_workspace_need", "spring_qlfc_from_host", "spring_qlfc_from_bwt", "spring_qlfc_download",
+    "spring_qlfc_get_info", "spring_qlfc_compress",
+]
+QLFC_RANK_TABLE, QLFC_RUN_TABLE = 32768, 8192  # SPRING_QLFC_RANK_TABLE, SPRING_QLFC_RUN_TABLE
+QLFC_PASSES = 6                                # SPRING_QLFC_PASSES
+QLFC_NOT_COMPRESSIBLE = -16                    # SPRING_QLFC_NOT_COMPRESSIBLE
+QLFC_EVENT_BYTES = 160                         # SPRING_QLFC_EVENT_BYTES
 
 
 class Opts(C.Structure):
@@ -203,8 +213,8 @@ NOT_INT = {"spring_reorder_last_error": C.c_char_p, "spring_synth_dna_bytes": C.
            "spring_reorder_default_opts": None, "spring_reorder_trim_pool": None, "spring_mg_comm_destroy": None}
 NOT_INT.update({p + "_destroy": None for p in ("spring_reorder", "spring_encoder", "spring_streams", "spring_decode",
                                                "spring_qualid", "spring_fastq_out", "spring_gzip", "spring_bwt",
-                                               "spring_unbwt", "spring_idcodec")})
-NOT_INT.update({p + "_workspace_need": C.c_uint64 for p in ("spring_bwt", "spring_unbwt", "spring_idcodec")})
+                                               "spring_unbwt", "spring_idcodec", "spring_qlfc")})
+NOT_INT.update({p + "_workspace_need": C.c_uint64 for p in ("spring_bwt", "spring_unbwt", "spring_idcodec", "spring_qlfc")})
 
 # spring_mg_allgather_fn (include/spring_reorder.h): host_buf, slice_off, slice_bytes, total_bytes, user -> 0 on success
 MG_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p)
@@ -364,8 +374,18 @@ def lib():
     L.spring_idcodec_download.argtypes = [vp, u8p, vp]
     L.spring_idcodec_symbols.argtypes = [vp, vp, vp]
     L.spring_idcodec_get_info.argtypes = [vp, C.POINTER(IdCodecInfo)]
+    L.spring_qlfc_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.spring_qlfc_destroy.argtypes = [vp]
+    L.spring_qlfc_set_state_tables.argtypes = [vp, u8p, u8p]
+    L.spring_qlfc_set_workspace_bytes.argtypes = [vp, C.c_uint64]
+    L.spring_qlfc_workspace_need.argtypes = [C.c_uint64, C.c_uint64]
+    L.spring_qlfc_from_host.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint64, vp]   # the last: spring_amd.qlfc.QlfcInfo *
+    L.spring_qlfc_from_bwt.argtypes = [vp, vp, vp]
+    L.spring_qlfc_download.argtypes = [vp, u8p, vp, vp]
+    L.spring_qlfc_get_info.argtypes = [vp, vp]
+    L.spring_qlfc_compress.argtypes = [vp, u8p, u8p, C.c_int32]
     for name in (EXPORTS + STREAMS_EXPORTS + DECODE_EXPORTS + QUALID_EXPORTS + FASTQ_OUT_EXPORTS + GZIP_EXPORTS
-                 + BWT_EXPORTS + UNBWT_EXPORTS + IDCODEC_EXPORTS):
+                 + BWT_EXPORTS + UNBWT_EXPORTS + IDCODEC_EXPORTS + QLFC_EXPORTS):
         getattr(L, name).restype = NOT_INT.get(name, C.c_int)
     _lib = L
     return L
