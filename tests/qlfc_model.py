@@ -75,20 +75,24 @@ def random_tables(seed):
 
 
 class _Coder:
-    """The range coder (rangecoder.h:73-129): 16-bit units, carries counted in ffnum."""
+    """The range coder (rangecoder.h:73-129): 16-bit units, carries counted in ffnum.  pend: the shifts that only
+    counted a pending unit; flushed[carry]: the pending units written out later, without and with a carry."""
 
     def __init__(self):
         self.low, self.range, self.ffnum, self.cache, self.out = 0, 0xffffffff, 0, 0, []
+        self.pend, self.flushed = 0, [0, 0]
 
     def shift_low(self):
         low32, carry = self.low & 0xffffffff, self.low >> 32
         if low32 < 0xffff0000 or carry:
             self.out.append((self.cache + carry) & 0xffff)
             self.out.extend([(carry - 1) & 0xffff] * self.ffnum)
+            self.flushed[carry] += self.ffnum
             self.ffnum = 0
             self.cache = low32 >> 16
         else:
             self.ffnum += 1
+            self.pend += 1
         self.low = (low32 << 16) & 0xffffffff
 
     def bit(self, b, p):
@@ -117,12 +121,9 @@ def log2(n):
 
 def chunk_ranks(data):
     """-> (runs as (byte, length), rank per run, the symbols in the order of the table header, maxRank)."""
-    runs = []
-    for b in data:
-        if runs and runs[-1][0] == b:
-            runs[-1][1] += 1
-        else:
-            runs.append([b, 1])
+    a = np.frombuffer(bytes(data), np.uint8)
+    heads = np.flatnonzero(np.concatenate(([True], a[1:] != a[:-1]))) if len(a) else np.zeros(0, np.int64)
+    runs = [[b, n] for b, n in zip(a[heads].tolist(), np.diff(np.append(heads, len(a))).tolist())]
     mtf, seen, ranks = list(range(256)), [], [0] * len(runs)
     for r in range(len(runs) - 1, -1, -1):      # backwards, run by run (qlfc.cpp:52-109)
         c = runs[r][0]
@@ -138,8 +139,12 @@ def chunk_ranks(data):
     return runs, ranks, order, (log2(len(order) - 1) if len(order) < 256 else 7)
 
 
-def encode_chunk(data, output_size, tables, stats=None):
-    """bsc_qlfc_static_encode (qlfc.cpp:448-752) -> the chunk's payload, or None where CheckEOB fires."""
+def encode_chunk(data, output_size, tables, stats=None, check=True):
+    """bsc_qlfc_static_encode (qlfc.cpp:448-752) -> the chunk's payload, or None where CheckEOB fires.  stats, a
+    dictionary, is added to by every chunk that is coded to its end: runs, events, the range coder's pend,
+    flush_nocarry and flush_carry, escaped (runs coded on the escape path) and esc_switches (changes between the two
+    rank paths) as sums; max_rank, symbols, lastev (the events in front of the last run) and margin (CheckEOB's
+    (output_size - 16) - bytes written, at the last run) as one entry per chunk.  check=False switches CheckEOB off."""
     rank_table, run_table = tables
     rows, mix = params()
     n = len(data)
@@ -175,9 +180,15 @@ def encode_chunk(data, output_size, tables, stats=None):
 
     rank_hist, run_hist = [0] * 256, [0] * 256
     ctx_rank0 = ctx_rank4 = ctx_run = avg_rank = 0
+    escaped = switches = lastev = margin = 0
+    was_escape = False
     for (c, run), rank in zip(runs, ranks):
-        if co.nbytes() >= output_size - 16:
+        if check and co.nbytes() >= output_size - 16:
             return None
+        lastev, margin = events, output_size - 16 - co.nbytes()
+        escaped += avg_rank >= 32
+        switches += (avg_rank >= 32) != was_escape
+        was_escape = avg_rank >= 32
         state = int(rank_table[ctx_run << 11 | ctx_rank4 << 3 | rank_hist[c]])
         if avg_rank < 32:
             if rank == 1:
@@ -223,10 +234,15 @@ def encode_chunk(data, output_size, tables, stats=None):
         ctx_rank0 = (ctx_rank0 << 1 | (rank == 0)) & 7
         ctx_rank4 = (ctx_rank4 << 2 | min(rank, 3)) & 0xff
         ctx_run = (ctx_run << 1 | (run < 3)) & 0xf
+    body = co.finish()                  # the three closing shifts count too
     if stats is not None:
-        stats["runs"] = stats.get("runs", 0) + len(runs)
-        stats["events"] = stats.get("events", 0) + events
-    return co.finish()
+        sums = dict(runs=len(runs), events=events, pend=co.pend, flush_nocarry=co.flushed[0], flush_carry=co.flushed[1],
+                    escaped=escaped, esc_switches=switches)
+        for key, v in sums.items():
+            stats[key] = stats.get(key, 0) + v
+        for key, v in dict(max_rank=max_rank, symbols=len(order), lastev=lastev, margin=margin).items():
+            stats.setdefault(key, []).append(v)
+    return body
 
 
 def num_chunks(n):
@@ -268,6 +284,14 @@ def compress(data, tables, stats=None):
         payload += body
         ptr += len(body)
     return bytes([k]) + table + payload, ptr
+
+
+def last_run_margin(data, tables):
+    """CheckEOB's margin (output_size - 16) - bytes written at the last run of a one-chunk segment, with the check
+    switched off: below 1 the segment is not compressible."""
+    stats = {}
+    encode_chunk(bytes(data), len(data) - 1, tables, stats, check=False)
+    return stats["margin"][0]
 
 
 # ---------------------------------------------------------------------------------------------- the real functions
@@ -320,9 +344,75 @@ def _cycle(total, bump):
     return b"".join(bytes([65 + r % 5]) * n for r, n in enumerate(lens))
 
 
+def _strips(n):
+    """n bytes in runs of 1000 over five letters: no run starts on a sampled position (1000 j = 1 mod 32 has no
+    solution), so the chunk rule counts nothing and takes the equal split."""
+    return (b"".join(bytes([65 + r % 5]) * 1000 for r in range(n // 1000 + 1)))[:n]
+
+
+def _marked(n):
+    """_strips(n) with a lone 'Z' on k + 1 sampled positions, the last of them the last sample there is,
+    1 + 32 (ns - 1): one more than k, so the sampled cut is taken, and only because of the last sample."""
+    k = num_chunks(n)
+    last = 1 + 32 * ((n - 2) // 32)
+    marks = [1 + 32 * (n * j // (k + 1) // 32) for j in range(1, k + 1)] + [last]
+    a = bytearray(_strips(n))
+    for p in marks:
+        a[p] = 90
+    return bytes(a)
+
+
+def run_segment(count, seed, first):
+    """A text of exactly `count` runs of 1 to 3 bytes over the four letters first .. first + 3, starting with `first`;
+    a single run is 40 bytes long, so that it is coded."""
+    rng = np.random.default_rng(seed)
+    steps, lens = rng.integers(1, 4, count), rng.integers(1, 4, count) if count > 1 else [40]
+    out, c = [], 0
+    for r in range(count):
+        out.append(bytes([first + c]) * int(lens[r]))
+        c = (c + int(steps[r])) % 4
+    return b"".join(out)
+
+
+# Inputs found by tools/qlfc_edge_search.py, per pair of state tables ("real": libbsc's; else random_tables(seed)).
+# pend: 3000 bytes over 9 letters, _letters(3000, 9, seed), whose coder flushes a pending unit without (n) and with (c)
+# a carry.  eob: _letters(n, k, seed), one chunk, CheckEOB's margin at the last run 0 (n odd: not compressible by one
+# comparison) and 1 (n even: coded by one unit).
+SEARCHED = {
+    "real": dict(pend_n=1004, pend_c=1994, eob_0=(1501, 114, 1000), eob_1=(1502, 68, 1003)),
+    101: dict(pend_n=1209, pend_c=1269, eob_0=(1501, 67, 1000), eob_1=(1502, 67, 1000)),
+    202: dict(pend_n=1032, pend_c=1220, eob_0=(1501, 67, 1001), eob_1=(1502, 67, 1001)),
+}
+ABSENT = {"no0": 0, "no127": 127, "no128": 128, "no255": 255}
+
+
+def table_cases(which):
+    """The names of the searched cases of one pair of tables."""
+    return tuple("%s_%s" % (kind, which) for kind in ("pend_n", "pend_c", "eob_0", "eob_1"))
+
+
+def _absent(c):
+    """Eight shuffles of the 255 other bytes, in runs of one to three."""
+    rng = np.random.default_rng(300 + c)
+    rest = np.array([b for b in range(256) if b != c], np.uint8)
+    return b"".join(bytes([int(b)]) * (1 + int(b) % 3) for _ in range(8) for b in rng.permutation(rest))
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
     rnd = lambda n, seed: np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8).tobytes()
+    if name.startswith(("pend_", "eob_")):
+        kind, which = name.rsplit("_", 1)
+        found = SEARCHED["real" if which == "real" else int(which)][kind]
+        return _letters(3000, 9, found) if kind.startswith("pend") else _letters(*found)
+    if name.startswith("esc"):
+        return _letters(5000, int(name[3:]), 6)
+    if name.startswith("eq"):
+        return _strips(int(name[2:]))
+    if name.startswith("smp"):
+        return _marked(int(name[3:]))
+    if name in ABSENT:
+        return _absent(ABSENT[name])
     if name.startswith("len"):
         return rnd(int(name[3:]), 1)
     if name.startswith("letters"):
@@ -342,6 +432,12 @@ def case(name):
         "bwt300000": lambda: bm.bwt(_mers(300000))[0],
         "random_a": lambda: rnd(262144, 5) + b"A" * 262144,
         "a_random": lambda: b"A" * 262144 + rnd(262144, 5),
+        "ring100": lambda: bytes(range(100)) * 50,
+        "desc256": lambda: bytes(range(255, -1, -1)) + b"".join(bytes([c]) * (c % 7 + 1) for c in range(256)) * 4,
+        "raw_coded": lambda: rnd(3000, 7) + b"A" * (262144 - 3000),
+        "coded_raw": lambda: b"A" * (262144 - 2144) + rnd(2144, 8),
+        "raw4": lambda: (rnd(2000, 9) + b"A" * (2 * MIB - 4000) + rnd(4000, 10) + b"C" * (2 * MIB - 4000) + rnd(2000, 12)),
+        "random262144": lambda: rnd(262144, 13),
     }[name]()
 
 
@@ -349,3 +445,36 @@ SMALL = ("len1", "len2", "len16", "len17", "a40", "ab32", "letters1", "letters2"
          "tail0", "all256", "all256runs", "random4096", "exp16", "bwt5000")
 MODEL_CASES = SMALL + ("a300000", "bwt300000", "cycle4e", "cycle4s", "cycle16e", "cycle16s")
 REF_ONLY_CASES = ("random_a", "a_random")     # about 3 * 10^6 events each: too slow for the Python model
+# The branches the cases above do not reach, every one coded under the real tables and under
+# random_tables(101) and (202); table_cases(which) adds what had to be searched for per pair of tables.
+MIB = 1 << 20
+CHUNK_SIZES = (262143, 262145, 262146, 4 * MIB - 1, 4 * MIB + 1)
+ESCAPE_CASES = ("esc100", "esc128", "esc129", "ring100")
+SYMBOL_CASES = ("letters4", "letters8", "no0", "no127", "no128", "no255", "desc256")
+SPLIT_CASES = tuple("eq%d" % n for n in CHUNK_SIZES) + tuple("smp%d" % n for n in CHUNK_SIZES[1:])
+RAW_CASES = ("raw_coded", "coded_raw", "raw4")
+EDGE_CASES = ESCAPE_CASES + SYMBOL_CASES + SPLIT_CASES + RAW_CASES
+ROLLBACK_CASE = "random262144"                # incompressible throughout: the real function only, as REF_ONLY_CASES
+
+# Batches of one-chunk segments with exact run counts, so that chunk boundaries fall on the 256-run tiles of the rank
+# pass (256, 512, 513, 768) and on the 64-run loads of the context walk.  Every segment has four letters of its own:
+# the first byte of a segment is absent from the one before, which a rank pass that looked one run too far would list.
+# The seeds of the 63- and 65-run segments (tools/qlfc_edge_search.py lanes) put the first event of the last run on
+# the last and on the first lane of a 64-event load of the range coder.
+RUN_ORDERS = ((256, 256, 1, 255, 512), (64, 64, 1, 63, 65, 128))
+RUN_SEEDS = {63: 58, 65: 13}
+
+
+def run_batch(counts):
+    return [run_segment(c, RUN_SEEDS.get(c, 40 + j), 65 + 4 * j) for j, c in enumerate(counts)]
+
+
+@functools.lru_cache(maxsize=None)
+def many_segments():
+    """1500 segments of 40 to 200 random bytes over 2 to 4 letters, every hundredth one empty: more than 1024 chunks."""
+    rng = np.random.default_rng(77)
+    segs = []
+    for j in range(1500):
+        n, k = int(rng.integers(40, 201)), int(rng.integers(2, 5))
+        segs.append(b"" if j % 100 == 99 else bytes((65 + rng.integers(0, k, n)).astype(np.uint8)))
+    return tuple(segs)

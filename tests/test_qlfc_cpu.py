@@ -28,7 +28,7 @@ def test_state_tables_are_read_from_the_library():
 
 
 @needs_ref
-@pytest.mark.parametrize("name", qm.MODEL_CASES)
+@pytest.mark.parametrize("name", qm.MODEL_CASES + qm.EDGE_CASES + qm.table_cases("real"))
 def test_model_equals_bsc_coder_compress(name):
     data = qm.case(name)
     want, rc = qm.ref_compress(data)
@@ -75,6 +75,105 @@ def test_cases_reach_what_they_are_for():
         assert [sizes[0] == sizes[1], sizes[2] == sizes[3]] == ([True, False] if name == "random_a" else [False, True])
         back, drc = qm.ref_decompress(coded, len(qm.case(name)))
         assert drc >= 0 and back == qm.case(name)
+
+
+def _sizes(coded):
+    """-> per chunk of a coded multi-chunk segment (input size, stored size)."""
+    v = struct.unpack_from("<%di" % (2 * coded[0]), coded, 1)
+    return list(zip(v[0::2], v[1::2]))
+
+
+@pytest.mark.parametrize("which", [pytest.param("real", marks=needs_ref), 101, 202])
+def test_edge_cases_reach_what_they_are_for(which):
+    """What each of EDGE_CASES and table_cases(which) is in the set for, read off the model's counters under the pair
+    of tables it is compared with on the device."""
+    tables = TABLES if which == "real" else qm.random_tables(which)
+    out = {}
+    for name in qm.EDGE_CASES + qm.table_cases(which):
+        stats = {}
+        coded, rc = qm.compress(qm.case(name), tables, stats)
+        out[name] = (coded, rc, stats)
+        print(name, len(qm.case(name)), "->", rc, stats)
+    # only the margin-0 case is not compressible: everything else compares bytes
+    for name, (coded, rc, _) in out.items():
+        assert (rc == qm.NOT_COMPRESSIBLE and coded == b"") if name == "eob_0_%s" % which else (rc == len(coded) > 0), name
+    # the range coder's pending units
+    st = out["pend_n_%s" % which][2]
+    assert st["pend"] >= 1 and st["flush_nocarry"] >= 1
+    st = out["pend_c_%s" % which][2]
+    assert st["pend"] >= 1 and st["flush_carry"] >= 1
+    # the escape path below 256 symbols, maxRank 6 and 7, and going back and forth between the two rank paths
+    for name, symbols, max_rank in (("esc100", 100, 6), ("esc128", 128, 6), ("esc129", 129, 7), ("ring100", 100, 6)):
+        st = out[name][2]
+        assert (st["symbols"], st["max_rank"]) == ([symbols], [max_rank]), name
+        assert 2 * st["escaped"] > st["runs"], name
+        assert st["esc_switches"] >= (100 if name == "esc100" else 1), name
+    assert out["ring100"][2]["escaped"] >= 5000 - 100   # rank 99 on every run but the last hundred
+    # symbol tables: 4 and 8 symbols, 255 (closed by listing the last symbol again) with either end and the middle
+    # absent, 256 in descending order
+    assert out["letters4"][2]["symbols"] == [4] and out["letters8"][2]["symbols"] == [8]
+    for name, absent in qm.ABSENT.items():
+        assert out[name][2]["symbols"] == [255] and absent not in qm.case(name), name
+    assert qm.chunk_ranks(qm.case("desc256"))[2] == list(range(255, -1, -1))
+    # the chunk rule around its thresholds
+    for n in qm.CHUNK_SIZES:
+        k = qm.num_chunks(n)
+        assert k == (1 if n < 262144 else 2 if n < 4 << 20 else 4)
+        data = qm.case("eq%d" % n)
+        equal = [n // k * p for p in range(k)]
+        assert len(data) == n and qm.split(data, k)[:-1] == equal
+        assert out["eq%d" % n][2]["symbols"] == [5] * k
+        if k == 1:
+            assert out["eq%d" % n][0][0] == 1
+            continue
+        assert n % k or n == 262146                  # the equal split leaves a rest wherever the size allows one
+        assert [a for a, _ in _sizes(out["eq%d" % n][0])] == [n // k] * (k - 1) + [n - n // k * (k - 1)]
+        data = qm.case("smp%d" % n)
+        a = np.frombuffer(data, np.uint8)
+        pos = np.arange(1, n, 32)
+        hits = pos[a[pos] != a[pos - 1]]
+        assert len(data) == n and len(hits) == k + 1 and hits[-1] == pos[-1] >= n - 32   # one more than k, the last sample
+        assert n % 32 not in (1, 2) or pos[-1] == n - 1 - (n % 32 == 1) * 31
+        cuts = qm.split(data, k)
+        assert cuts == [0] + [int(h) for h in hits[:k - 1]] + [n] and cuts[:-1] != equal
+        assert qm.split(data[:int(pos[-1])] + bytes([data[int(pos[-1]) - 1]]) * (n - int(pos[-1])), k)[:-1] == equal
+        assert [a for a, _ in _sizes(out["smp%d" % n][0])] == list(np.diff(cuts))
+    # raw chunks beside coded ones
+    for name, raw in (("raw_coded", [True, False]), ("coded_raw", [False, True]), ("raw4", [True, False, True, False])):
+        sizes = _sizes(out[name][0])
+        assert [a == b for a, b in sizes] == raw and out[name][2]["raw"] == sum(raw), name
+        assert all(b < a // 8 for (a, b), r in zip(sizes, raw) if not r), name
+    assert not any("raw" in out[name][2] for name in out if name not in qm.RAW_CASES)
+    # CheckEOB at the last run, one unit either side
+    for name, margin in (("eob_0_%s" % which, 0), ("eob_1_%s" % which, 1)):
+        assert qm.num_chunks(len(qm.case(name))) == 1 and qm.last_run_margin(qm.case(name), tables) == margin
+    assert out["eob_1_%s" % which][2]["margin"] == [1]
+
+
+@needs_ref
+def test_the_rollback_case_is_not_compressible():
+    """262144 random bytes: two chunks, the first stored raw, the second fails where it can no longer be stored."""
+    data = qm.case(qm.ROLLBACK_CASE)
+    assert qm.num_chunks(len(data)) == 2 and qm.ref_compress(data) == (b"", qm.NOT_COMPRESSIBLE)
+    cut = qm.split(data, 2)[1]
+    assert qm.ref_compress(data[:cut])[1] == qm.NOT_COMPRESSIBLE and qm.ref_compress(data[cut:])[1] == qm.NOT_COMPRESSIBLE
+
+
+def test_run_batches_and_many_segments_are_what_they_say():
+    for counts in qm.RUN_ORDERS:
+        segs = qm.run_batch(counts)
+        assert [len(qm.chunk_ranks(s)[0]) for s in segs] == list(counts)
+        assert all(b[0] not in a for a, b in zip(segs, segs[1:]))
+        assert all(qm.compress(s, qm.random_tables(101))[1] > 0 for s in segs)
+    lanes = {}
+    for count, seg in zip(qm.RUN_ORDERS[1], qm.run_batch(qm.RUN_ORDERS[1])):
+        stats = {}
+        qm.encode_chunk(seg, len(seg) - 1, qm.random_tables(101), stats)
+        lanes[count] = stats["lastev"][0] % 64
+    assert lanes[63] == 63 and lanes[65] == 0
+    segs = qm.many_segments()
+    assert len(segs) == 1500 and [j for j, s in enumerate(segs) if not s] == list(range(99, 1500, 100))
+    assert all(40 <= len(s) <= 200 and 2 <= len(set(s)) <= 4 for s in segs if s)
 
 
 def test_parameter_table_and_slot_numbering():
