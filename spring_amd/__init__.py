@@ -14,3 +14,4 @@ from .bwt import BwtStage  # noqa: F401,E402
 from .unbwt import UnbwtStage  # noqa: F401,E402
 from .idcodec import IdCodecStage  # noqa: F401,E402
 from .qlfc import QlfcStage  # noqa: F401,E402
+from .bsc import BscStage  # noqa: F401,E402

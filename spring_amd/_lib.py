@@ -93,6 +93,16 @@ QLFC_PASSES = 6                                # SPRING_QLFC_PASSES
 QLFC_NOT_COMPRESSIBLE = -16                    # SPRING_QLFC_NOT_COMPRESSIBLE
 QLFC_EVENT_BYTES = 160                         # SPRING_QLFC_EVENT_BYTES
 
+# include/spring_bsc.h: a list of its own as well
+BSC_EXPORTS = [
+    "spring_bsc_create", "spring_bsc_destroy", "spring_bsc_from_streams", "spring_bsc_from_qualid", "spring_bsc_from_host",
+    "spring_bsc_download", "spring_bsc_files", "spring_bsc_get_info", "spring_bsc_adler32", "spring_bsc_compress",
+]
+BSC_HEADER_BYTES = 28                          # SPRING_BSC_HEADER_BYTES
+BSC_PASSES = 3                                 # SPRING_BSC_PASSES
+BSC_BLOCKS, BSC_FILE, BSC_STR_ARRAY = 0, 1, 2  # framing: SPRING_BSC_BLOCKS, _FILE, _STR_ARRAY
+BSC_CODED, BSC_STORED_SMALL, BSC_STORED_CODER, BSC_STORED_NO_GAIN = 0, 1, 2, 3   # block_kind
+
 
 class Opts(C.Structure):
     _fields_ = [("device", C.c_int32), ("num_chains", C.c_uint32), ("num_thr", C.c_int32),
@@ -213,7 +223,7 @@ NOT_INT = {"spring_reorder_last_error": C.c_char_p, "spring_synth_dna_bytes": C.
            "spring_reorder_default_opts": None, "spring_reorder_trim_pool": None, "spring_mg_comm_destroy": None}
 NOT_INT.update({p + "_destroy": None for p in ("spring_reorder", "spring_encoder", "spring_streams", "spring_decode",
                                                "spring_qualid", "spring_fastq_out", "spring_gzip", "spring_bwt",
-                                               "spring_unbwt", "spring_idcodec", "spring_qlfc")})
+                                               "spring_unbwt", "spring_idcodec", "spring_qlfc", "spring_bsc")})
 NOT_INT.update({p + "_workspace_need": C.c_uint64 for p in ("spring_bwt", "spring_unbwt", "spring_idcodec", "spring_qlfc")})
 
 # spring_mg_allgather_fn (include/spring_reorder.h): host_buf, slice_off, slice_bytes, total_bytes, user -> 0 on success
@@ -384,8 +394,18 @@ def lib():
     L.spring_qlfc_download.argtypes = [vp, u8p, vp, vp]
     L.spring_qlfc_get_info.argtypes = [vp, vp]
     L.spring_qlfc_compress.argtypes = [vp, u8p, u8p, C.c_int32]
+    L.spring_bsc_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.spring_bsc_destroy.argtypes = [vp]
+    L.spring_bsc_from_streams.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]   # the last: spring_amd.bsc.BscInfo *
+    L.spring_bsc_from_qualid.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_uint64, vp]
+    L.spring_bsc_from_host.argtypes = [vp, vp, vp, u8p, C.c_uint64, vp, C.c_uint64, C.c_int32, vp, C.c_uint64, vp]
+    L.spring_bsc_download.argtypes = [vp, u8p, vp, vp, vp]
+    L.spring_bsc_files.argtypes = [vp, vp, vp, vp]
+    L.spring_bsc_get_info.argtypes = [vp, vp]
+    L.spring_bsc_adler32.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint64, vp]
+    L.spring_bsc_compress.argtypes = [vp, vp, vp, u8p, u8p, C.c_int32]
     for name in (EXPORTS + STREAMS_EXPORTS + DECODE_EXPORTS + QUALID_EXPORTS + FASTQ_OUT_EXPORTS + GZIP_EXPORTS
-                 + BWT_EXPORTS + UNBWT_EXPORTS + IDCODEC_EXPORTS + QLFC_EXPORTS):
+                 + BWT_EXPORTS + UNBWT_EXPORTS + IDCODEC_EXPORTS + QLFC_EXPORTS + BSC_EXPORTS):
         getattr(L, name).restype = NOT_INT.get(name, C.c_int)
     _lib = L
     return L

@@ -716,7 +716,9 @@ int bwt_view(spring_bwt_ctx *ctx, BwtView *v) {
   if (!ctx || !v) return fail(SPRING_REORDER_E_ARG, "NULL argument");
   if (!ctx->have) return fail(SPRING_REORDER_E_STATE, "nothing transformed yet");
   *v = BwtView{ctx->dev, ctx->info.num_segments, ctx->info.bytes, ctx->out.as<uint8_t>(), ctx->primary.as<int32_t>(),
-               ctx->off.data()};
+               ctx->off.data(), ctx->nidx.as<int32_t>(), ctx->indexes.as<int32_t>(), ctx->seg_stream.data(),
+               ctx->seg_block.data(), ctx->seg_cut.data()};
   return 0;
 }
+int bwt_device(spring_bwt_ctx *ctx) { return ctx->dev; }
 }  // namespace sr

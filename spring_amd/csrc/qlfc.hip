@@ -501,6 +501,8 @@ struct spring_qlfc_ctx {
   std::vector<int32_t> status;
   std::vector<std::unique_ptr<DBuf>> out;   // per sub-batch: its coded bytes
   std::vector<uint64_t> out_bytes;
+  bool have_view = false;            // the device copies a QlfcView hands out
+  DBuf v_src, v_off, v_status;
 };
 
 namespace {
@@ -511,6 +513,10 @@ void drop_result(spring_qlfc_ctx *ctx) {
   ctx->out_bytes.clear();
   ctx->coded_off.clear();
   ctx->status.clear();
+  ctx->have_view = false;
+  ctx->v_src.release();
+  ctx->v_off.release();
+  ctx->v_status.release();
   memset(&ctx->info, 0, sizeof(ctx->info));
 }
 
@@ -936,3 +942,37 @@ int spring_qlfc_compress(spring_qlfc_ctx *ctx, const uint8_t *in, uint8_t *out, 
 }
 
 }  // extern "C"
+
+namespace sr {
+int qlfc_view(spring_qlfc_ctx *ctx, QlfcView *v) {
+  if (!ctx || !v) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  if (!ctx->have) return fail(SPRING_REORDER_E_STATE, "nothing coded yet");
+  const uint64_t S = ctx->info.num_segments;
+  if (!ctx->have_view) {
+    const int r = stream_begin(ctx->dev, &ctx->st);
+    if (r) return r;
+    const int dev = ctx->dev;
+    std::vector<uint64_t> src(S + 1, 0);
+    uint64_t start = 0;   // the coded bytes in front of sub-batch b
+    for (uint64_t s = 0, b = 0; s < S; s++) {
+      while (b + 1 < ctx->out.size() && ctx->coded_off[s] >= start + ctx->out_bytes[b]) start += ctx->out_bytes[b++];
+      if (!ctx->out.empty()) src[s] = reinterpret_cast<uint64_t>(ctx->out[b]->as<uint8_t>()) + (ctx->coded_off[s] - start);
+    }
+    DALLOC(ctx->v_src, (S + 1) * 8);
+    DALLOC(ctx->v_off, (S + 1) * 8);
+    DALLOC(ctx->v_status, S * 4);
+    HIPCHK(hipMemcpyAsync(ctx->v_src.p, src.data(), (S + 1) * 8, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipMemcpyAsync(ctx->v_off.p, ctx->coded_off.data(), (S + 1) * 8, hipMemcpyHostToDevice, ctx->st));
+    if (S) HIPCHK(hipMemcpyAsync(ctx->v_status.p, ctx->status.data(), S * 4, hipMemcpyHostToDevice, ctx->st));
+    HIPCHK(hipStreamSynchronize(ctx->st));   // src is the host's until here
+    ctx->have_view = true;
+  }
+  *v = QlfcView{ctx->dev, S, ctx->info.bytes_out, ctx->coded_off.data(), ctx->status.data(), ctx->v_src.as<uint64_t>(),
+                ctx->v_off.as<uint64_t>(), ctx->v_status.as<int32_t>()};
+  return 0;
+}
+int qlfc_device(spring_qlfc_ctx *ctx, bool *have_tables) {
+  if (have_tables) *have_tables = ctx->have_tables;
+  return ctx->dev;
+}
+}  // namespace sr
