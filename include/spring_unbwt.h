@@ -29,6 +29,9 @@
  *   from_host   offsets start at 0, do not decrease and end at nbytes; NULL offsets mean one segment.
  *   from_bwt    the result of a finished block-sort context (spring_bwt.h), read in place in HBM and left as it was:
  *               its segments, offsets and primary indexes.
+ *   from_unqlfc the decoded segments of a finished QLFC decoder context (spring_unqlfc.h), read where they lie in HBM
+ *               and left as they were, with one primary index per segment from the caller (the block headers hold
+ *               them); a segment that context left empty takes primary index 0.
  *
  * Refused before any result: offsets that do not start at 0, decrease or do not end at nbytes, a NULL buffer with
  * nbytes > 0, a NULL primary array, a primary index out of range, a block-sort context on another device, a segment
@@ -45,6 +48,7 @@
 #include <stdint.h>
 
 #include "spring_bwt.h"
+#include "spring_unqlfc.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -83,6 +87,8 @@ int spring_unbwt_set_head_spacing(spring_unbwt_ctx *ctx, uint32_t head_spacing);
 int spring_unbwt_from_host(spring_unbwt_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const uint64_t *seg_off,
                            const int32_t *primary, uint64_t num_segments, spring_unbwt_info *info);
 int spring_unbwt_from_bwt(spring_unbwt_ctx *ctx, spring_bwt_ctx *bwt, spring_unbwt_info *info);
+int spring_unbwt_from_unqlfc(spring_unbwt_ctx *ctx, spring_unqlfc_ctx *unqlfc, const int32_t *primary /* [num_segments] */,
+                             spring_unbwt_info *info);
 
 /* text: info.bytes bytes, the segments back to back; seg_off: info.num_segments + 1 offsets into it.  Either may be
  * NULL. */

@@ -15,3 +15,4 @@ from .unbwt import UnbwtStage  # noqa: F401,E402
 from .idcodec import IdCodecStage  # noqa: F401,E402
 from .qlfc import QlfcStage  # noqa: F401,E402
 from .bsc import BscStage  # noqa: F401,E402
+from .unqlfc import UnqlfcStage  # noqa: F401,E402

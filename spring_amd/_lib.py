@@ -72,7 +72,7 @@ BWT_SRC_QUALITY, BWT_SRC_ID = -2, -3  # SPRING_BWT_SRC_QUALITY, SPRING_BWT_SRC_I
 UNBWT_EXPORTS = [
     "spring_unbwt_create", "spring_unbwt_destroy", "spring_unbwt_set_workspace_bytes", "spring_unbwt_workspace_need",
     "spring_unbwt_set_head_spacing", "spring_unbwt_from_host", "spring_unbwt_from_bwt", "spring_unbwt_download",
-    "spring_unbwt_get_info", "spring_unbwt_decode_inplace",
+    "spring_unbwt_get_info", "spring_unbwt_decode_inplace", "spring_unbwt_from_unqlfc",
 ]
 UNBWT_PASSES = 6  # SPRING_UNBWT_PASSES
 
@@ -92,6 +92,15 @@ QLFC_RANK_TABLE, QLFC_RUN_TABLE = 32768, 8192  # SPRING_QLFC_RANK_TABLE, SPRING_
 QLFC_PASSES = 6                                # SPRING_QLFC_PASSES
 QLFC_NOT_COMPRESSIBLE = -16                    # SPRING_QLFC_NOT_COMPRESSIBLE
 QLFC_EVENT_BYTES = 160                         # SPRING_QLFC_EVENT_BYTES
+
+# include/spring_unqlfc.h: a list of its own as well
+UNQLFC_EXPORTS = [
+    "spring_unqlfc_create", "spring_unqlfc_destroy", "spring_unqlfc_set_state_tables", "spring_unqlfc_set_workspace_bytes",
+    "spring_unqlfc_workspace_need", "spring_unqlfc_from_host", "spring_unqlfc_from_qlfc", "spring_unqlfc_download",
+    "spring_unqlfc_get_info", "spring_unqlfc_decompress",
+]
+UNQLFC_PASSES = 3                              # SPRING_UNQLFC_PASSES
+UNQLFC_MODEL_BYTES = 1619200                   # SPRING_UNQLFC_MODEL_BYTES
 
 # include/spring_bsc.h: a list of its own as well
 BSC_EXPORTS = [
@@ -223,8 +232,10 @@ NOT_INT = {"spring_reorder_last_error": C.c_char_p, "spring_synth_dna_bytes": C.
            "spring_reorder_default_opts": None, "spring_reorder_trim_pool": None, "spring_mg_comm_destroy": None}
 NOT_INT.update({p + "_destroy": None for p in ("spring_reorder", "spring_encoder", "spring_streams", "spring_decode",
                                                "spring_qualid", "spring_fastq_out", "spring_gzip", "spring_bwt",
-                                               "spring_unbwt", "spring_idcodec", "spring_qlfc", "spring_bsc")})
-NOT_INT.update({p + "_workspace_need": C.c_uint64 for p in ("spring_bwt", "spring_unbwt", "spring_idcodec", "spring_qlfc")})
+                                               "spring_unbwt", "spring_idcodec", "spring_qlfc", "spring_bsc",
+                                               "spring_unqlfc")})
+NOT_INT.update({p + "_workspace_need": C.c_uint64 for p in ("spring_bwt", "spring_unbwt", "spring_idcodec", "spring_qlfc",
+                                                             "spring_unqlfc")})
 
 # spring_mg_allgather_fn (include/spring_reorder.h): host_buf, slice_off, slice_bytes, total_bytes, user -> 0 on success
 MG_ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p)
@@ -375,6 +386,7 @@ def lib():
     L.spring_unbwt_download.argtypes = [vp, u8p, vp]
     L.spring_unbwt_get_info.argtypes = [vp, C.POINTER(UnbwtInfo)]
     L.spring_unbwt_decode_inplace.argtypes = [vp, u8p, C.c_int32, C.c_int32, C.c_uint8, vp]
+    L.spring_unbwt_from_unqlfc.argtypes = [vp, vp, vp, C.POINTER(UnbwtInfo)]
     L.spring_idcodec_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_idcodec_destroy.argtypes = [vp]
     L.spring_idcodec_set_workspace_bytes.argtypes = [vp, C.c_uint64]
@@ -394,6 +406,16 @@ def lib():
     L.spring_qlfc_download.argtypes = [vp, u8p, vp, vp]
     L.spring_qlfc_get_info.argtypes = [vp, vp]
     L.spring_qlfc_compress.argtypes = [vp, u8p, u8p, C.c_int32]
+    L.spring_unqlfc_create.argtypes = [C.c_int32, C.POINTER(vp)]
+    L.spring_unqlfc_destroy.argtypes = [vp]
+    L.spring_unqlfc_set_state_tables.argtypes = [vp, u8p, u8p]
+    L.spring_unqlfc_set_workspace_bytes.argtypes = [vp, C.c_uint64]
+    L.spring_unqlfc_workspace_need.argtypes = [C.c_uint64, C.c_uint64]
+    L.spring_unqlfc_from_host.argtypes = [vp, u8p, C.c_uint64, vp, vp, C.c_uint64, vp]   # the last: spring_amd.unqlfc.UnqlfcInfo *
+    L.spring_unqlfc_from_qlfc.argtypes = [vp, vp, vp]
+    L.spring_unqlfc_download.argtypes = [vp, u8p, vp]
+    L.spring_unqlfc_get_info.argtypes = [vp, vp]
+    L.spring_unqlfc_decompress.argtypes = [vp, u8p, C.c_int32, u8p, C.c_int32]
     L.spring_bsc_create.argtypes = [C.c_int32, C.POINTER(vp)]
     L.spring_bsc_destroy.argtypes = [vp]
     L.spring_bsc_from_streams.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]   # the last: spring_amd.bsc.BscInfo *
@@ -405,7 +427,7 @@ def lib():
     L.spring_bsc_adler32.argtypes = [vp, u8p, C.c_uint64, vp, C.c_uint64, vp]
     L.spring_bsc_compress.argtypes = [vp, vp, vp, u8p, u8p, C.c_int32]
     for name in (EXPORTS + STREAMS_EXPORTS + DECODE_EXPORTS + QUALID_EXPORTS + FASTQ_OUT_EXPORTS + GZIP_EXPORTS
-                 + BWT_EXPORTS + UNBWT_EXPORTS + IDCODEC_EXPORTS + QLFC_EXPORTS + BSC_EXPORTS):
+                 + BWT_EXPORTS + UNBWT_EXPORTS + IDCODEC_EXPORTS + QLFC_EXPORTS + UNQLFC_EXPORTS + BSC_EXPORTS):
         getattr(L, name).restype = NOT_INT.get(name, C.c_int)
     _lib = L
     return L

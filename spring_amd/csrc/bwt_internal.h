@@ -1,6 +1,6 @@
-// spring_amd/csrc/bwt_internal.h -- what the stages behind the block sort (unbwt.hip, qlfc.hip, bsc_frame.hip) need from
-// a finished block-sort or QLFC context without a round trip through the host: the device buffers of its result and
-// the segment offsets.  Internal to the library.
+// spring_amd/csrc/bwt_internal.h -- what the stages behind the block sort (unbwt.hip, qlfc.hip, bsc_frame.hip,
+// unqlfc.hip) need from a finished block-sort, QLFC or QLFC decoder context without a round trip through the host: the
+// device buffers of its result and the segment offsets.  Internal to the library.
 #ifndef SPRING_BWT_INTERNAL_H_
 #define SPRING_BWT_INTERNAL_H_
 
@@ -8,6 +8,7 @@
 
 #include "spring_bwt.h"
 #include "spring_qlfc.h"
+#include "spring_unqlfc.h"
 
 namespace sr {
 
@@ -33,11 +34,20 @@ struct QlfcView {
   const uint64_t *d_src;       // device, one per segment: the device address of its coded bytes
   const uint64_t *d_off;       // device: coded_off
   const int32_t *d_status;     // device: status
+  const uint64_t *in_off;      // host: num_segments + 1 offsets of the segments as they came in
 };
 // Fails unless the context holds a result.  The device copies of the offsets and the status are made on the first call
 // behind a result and go with it.
 int qlfc_view(spring_qlfc_ctx *ctx, QlfcView *v);
 int qlfc_device(spring_qlfc_ctx *ctx, bool *have_tables);   // with or without a result
+
+struct UnqlfcView {
+  int dev;
+  uint64_t num_segments, bytes;
+  const uint64_t *off;         // host: num_segments + 1 offsets into out
+  const uint8_t *out;          // device: the decoded segments back to back
+};
+int unqlfc_view(spring_unqlfc_ctx *ctx, UnqlfcView *v);   // fails unless the context holds a result
 
 }  // namespace sr
 #endif

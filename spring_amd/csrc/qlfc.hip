@@ -498,6 +498,7 @@ struct spring_qlfc_ctx {
   DBuf rank_tab, run_tab;
   spring_qlfc_info info;
   std::vector<uint64_t> coded_off;   // num_segments + 1
+  std::vector<uint64_t> in_off;      // num_segments + 1: the segments as they came in
   std::vector<int32_t> status;
   std::vector<std::unique_ptr<DBuf>> out;   // per sub-batch: its coded bytes
   std::vector<uint64_t> out_bytes;
@@ -512,6 +513,7 @@ void drop_result(spring_qlfc_ctx *ctx) {
   ctx->out.clear();
   ctx->out_bytes.clear();
   ctx->coded_off.clear();
+  ctx->in_off.clear();
   ctx->status.clear();
   ctx->have_view = false;
   ctx->v_src.release();
@@ -783,6 +785,7 @@ int code_batch(spring_qlfc_ctx *ctx, const std::vector<uint64_t> &off, const std
   HIPCHK(hipMemcpyAsync(d_off.p, off.data(), (S + 1) * 8, hipMemcpyHostToDevice, st));
   if (S) HIPCHK(hipMemcpyAsync(d_src.p, src.data(), S * 8, hipMemcpyHostToDevice, st));
   ctx->coded_off.assign(1, 0);
+  ctx->in_off = off;
   for (uint64_t first = 0; first < S;) {
     uint64_t count = qlfc::take_segments(off.data(), S, first, budget);
     if (count == 0)
@@ -968,7 +971,7 @@ int qlfc_view(spring_qlfc_ctx *ctx, QlfcView *v) {
     ctx->have_view = true;
   }
   *v = QlfcView{ctx->dev, S, ctx->info.bytes_out, ctx->coded_off.data(), ctx->status.data(), ctx->v_src.as<uint64_t>(),
-                ctx->v_off.as<uint64_t>(), ctx->v_status.as<int32_t>()};
+                ctx->v_off.as<uint64_t>(), ctx->v_status.as<int32_t>(), ctx->in_off.data()};
   return 0;
 }
 int qlfc_device(spring_qlfc_ctx *ctx, bool *have_tables) {

@@ -551,6 +551,30 @@ int spring_unbwt_from_bwt(spring_unbwt_ctx *ctx, spring_bwt_ctx *bwt_ctx, spring
   return r;
 }
 
+int spring_unbwt_from_unqlfc(spring_unbwt_ctx *ctx, spring_unqlfc_ctx *unqlfc_ctx, const int32_t *primary, spring_unbwt_info *info) {
+  if (!ctx || !unqlfc_ctx) return fail(SPRING_REORDER_E_ARG, "NULL argument");
+  (void)hipSetDevice(ctx->dev);
+  drop_result(ctx);
+  sr::UnqlfcView V;
+  int r = sr::unqlfc_view(unqlfc_ctx, &V);
+  if (r) return r;
+  if (V.dev != ctx->dev) return fail(SPRING_REORDER_E_ARG, "QLFC decoder and inverse contexts live on different devices");
+  const uint64_t S = V.num_segments;
+  if (S && !primary) return fail(SPRING_REORDER_E_ARG, "NULL primary indexes");
+  if ((r = stream_begin(ctx->dev, &ctx->st))) return r;
+  const int dev = ctx->dev;
+  DBuf d_prim;
+  DALLOC(d_prim, S * 4);
+  if (S) HIPCHK(hipMemcpyAsync(d_prim.p, primary, S * 4, hipMemcpyHostToDevice, ctx->st));
+  ctx->off.assign(V.off, V.off + S + 1);
+  std::vector<uint64_t> src(S);
+  for (uint64_t s = 0; s < S; s++) src[s] = reinterpret_cast<uint64_t>(V.out + V.off[s]);
+  r = invert(ctx, src, d_prim.as<int32_t>(), primary, info);
+  if (ctx->st) (void)hipStreamSynchronize(ctx->st);
+  if (r) drop_result(ctx);
+  return r;
+}
+
 int spring_unbwt_get_info(spring_unbwt_ctx *ctx, spring_unbwt_info *info) {
   if (!ctx || !info) return fail(SPRING_REORDER_E_ARG, "NULL argument");
   if (!ctx->have) return fail(SPRING_REORDER_E_STATE, "nothing inverted yet");

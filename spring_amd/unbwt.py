@@ -8,6 +8,7 @@ import numpy as np
 from . import _lib
 from ._stage import Stage, chk
 from .bwt import BwtStage
+from .unqlfc import UnqlfcStage
 
 PASSES = ("keys", "sort", "scatter", "walk", "rank", "write")   # info["ms_pass"]
 
@@ -32,7 +33,8 @@ class UnbwtStage(Stage):
         chk(self._L.spring_unbwt_set_head_spacing(self._h, head_spacing))
 
     def invert(self, src, seg_off=None, primary=None):
-        """src: a BwtStage holding a result.  Or bytes / a uint8 array with primary: one primary index per segment (an
+        """src: a BwtStage holding a result.  Or an UnqlfcStage holding a result, with primary: one primary index per
+        segment.  Or bytes / a uint8 array with primary: one primary index per segment (an
         int for one segment) and seg_off: num_segments + 1 offsets from 0 to len(src) that do not decrease (None: one
         segment).  -> info."""
         self.info = None
@@ -40,6 +42,15 @@ class UnbwtStage(Stage):
             if seg_off is not None or primary is not None:
                 raise ValueError("seg_off and primary are for host buffers; a BwtStage brings its own")
             return self._run("from_bwt", src._h)
+        if isinstance(src, UnqlfcStage):   # the decoded segments where they lie; the primary indexes from the caller
+            if seg_off is not None:
+                raise ValueError("seg_off is for host buffers; an UnqlfcStage brings its own segments")
+            if primary is None:
+                raise ValueError("decoded segments need their primary indexes")
+            prim = np.ascontiguousarray(np.atleast_1d(primary), dtype=np.int32)
+            if src.info is None or len(prim) != src.info["num_segments"]:
+                raise ValueError("one primary index per decoded segment")
+            return self._run("from_unqlfc", src._h, prim.ctypes.data if len(prim) else None)
         a = src if isinstance(src, np.ndarray) else np.frombuffer(src, np.uint8)
         a = np.ascontiguousarray(a, np.uint8)
         off = None if seg_off is None else np.ascontiguousarray(seg_off, dtype=np.uint64)

@@ -11,6 +11,9 @@ be looked for, under one pair of state tables.  CPU only: it runs tests/qlfc_mod
   qlfc_edge_search.py TABLES lanes [--first S] [--count N]
       seeds of run_segment(63, seed, .) and run_segment(65, seed, .) in the second order of RUN_ORDERS whose last run's
       first event is event 63 and event 0 modulo 64 of its chunk (the number of events does not depend on the tables)
+  qlfc_edge_search.py TABLES units [--first S] [--count N] [--jobs J]
+      (n, seed) of _letters(n, 9, seed), n = 1000 .. 1063, whose payload holds a multiple of 64 units (last) or one
+      more (first): the decoder's last unit is the last or the first of a 64-unit load (tests/unqlfc_model.UNIT_CASES)
 
 TABLES is `real` (libbsc's tables out of oracle/_ref/libref_units.so) or the seed of qlfc_model.random_tables.  Every
 line printed is a candidate; SEARCHED and RUN_SEEDS hold one of each kind."""
@@ -39,6 +42,10 @@ def _pend(seed):
     return seed, rc, stats.get("pend", 0), stats.get("flush_nocarry", 0), stats.get("flush_carry", 0)
 
 
+def _units(job):
+    return job, len(qm.encode_chunk(qm._letters(job[0], 9, job[1]), job[0], TABLES, check=False)) // 2
+
+
 def _margin(job):
     return job, qm.last_run_margin(qm._letters(*job), TABLES)
 
@@ -46,7 +53,7 @@ def _margin(job):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("tables")
-    ap.add_argument("kind", choices=("pend", "eob", "lanes"))
+    ap.add_argument("kind", choices=("pend", "eob", "lanes", "units"))
     ap.add_argument("--first", type=int, default=1000)
     ap.add_argument("--count", type=int, default=400)
     ap.add_argument("--jobs", type=int, default=4)
@@ -62,6 +69,11 @@ def main():
                     print("lanes: %d runs, seed %d, lastev %d" % (count, seed, stats["lastev"][0]), flush=True)
         return
     with multiprocessing.Pool(args.jobs, _init, (args.tables,)) as pool:
+        if args.kind == "units":
+            for job, units in pool.imap(_units, [(n, s) for s in seeds for n in range(1000, 1064)], 8):
+                if units % 64 < 2:
+                    print("units_%s (n, seed) = %r units %d" % ("first" if units % 64 else "last", job, units), flush=True)
+            return
         if args.kind == "pend":
             for seed, rc, pend, nocarry, carry in pool.imap(_pend, seeds, 8):
                 if nocarry or carry:
