@@ -14,7 +14,7 @@ SOURCES = ["reorder_kernels.hip", "reorder_pipeline.cpp", "reorder_files.cpp", "
 HEADERS = ["reorder_device.h", "reorder_internal.h", "reorder_round_mc.h", "synth_common.h", "call_reorder.h",
            "encoder_internal.h", "streams_internal.h", "fastq_out_internal.h", "dict_build.h", "strand_filter.h",
            "gzip_codes.h", "bwt_plan.h", "bwt_internal.h", "unbwt_plan.h", "stage_host.h", "qlfc_plan.h", "qlfc_params.h",
-           "bsc_frame_plan.h", "unqlfc_plan.h"]
+           "bsc_frame_plan.h", "unqlfc_plan.h", "copy_words.h"]
 PUBLIC_HEADERS = ["spring_reorder.h", "spring_encoder.h", "spring_streams.h", "spring_decode.h", "spring_qualid.h",
                   "spring_fastq_out.h", "spring_gzip.h", "spring_bwt.h", "spring_unbwt.h", "spring_idcodec.h",
                   "spring_qlfc.h", "spring_bsc.h", "spring_unqlfc.h"]

@@ -7,7 +7,8 @@
 //   2  plan      per block the outcome of bsc_compress's store rule and the lengths of its pieces; per file its header;
 //                an exclusive scan (rocPRIM) gives every piece its place; the headers' first 20 bytes, the cut headers
 //                and the count bytes go to a small table.  The host reads the total and the four outcome counts
-//   3  assembly  the destination-driven copy: one lane per 16-byte word of the output walks the pieces that overlap it
+//   3  assembly  the destination-driven copy: one lane per 16-byte word of the output finds its first piece (last_le
+//                of copy_words.h) and walks the pieces that overlap it; the loads are its own (absolute addresses)
 //   1' sums      Adler-32 of every coded body, from the output; then one lane per block writes the last 8 bytes of its
 //                header: the body's sum and the sum of the 24 bytes in front
 //
@@ -21,6 +22,7 @@
 
 #include "bsc_frame_plan.h"
 #include "bwt_internal.h"
+#include "copy_words.h"
 #include "fastq_out_internal.h"
 #include "reorder_internal.h"
 #include "spring_bsc.h"
@@ -45,16 +47,6 @@ using bscf::TILE;
 __device__ __forceinline__ uint64_t mn(uint64_t a, uint64_t b) { return a < b ? a : b; }
 __device__ __forceinline__ uint64_t mx(uint64_t a, uint64_t b) { return a > b ? a : b; }
 
-// the last entry of a[0 .. n) that is <= x (a[0] <= x, a ascending)
-__device__ __forceinline__ uint64_t last_le(const uint64_t *a, uint64_t n, uint64_t x) {
-  uint64_t lo = 0, hi = n - 1;
-  for (int it = 0; it < 64 && lo < hi; it++) {
-    const uint64_t mid = lo + (hi - lo + 1) / 2;
-    if (a[mid] <= x) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // ------------------------------------------------------------------ 1: segmented Adler-32
 // The segments a sum pass walks: segment s is len[s] bytes at base + addr[s]; tfirst[s]: its first tile.
 struct Segs {
@@ -71,7 +63,7 @@ __global__ __launch_bounds__(256) void k_tiles(Segs G, uint2 *__restrict__ tiles
   __shared__ uint32_t sh[2][4];
   const uint64_t t = blockIdx.x;
   if (G.S == 0 || t >= G.tfirst[G.S]) return;   // uniform
-  const uint64_t s = last_le(G.tfirst, G.S, t);
+  const uint64_t s = last_le(G.S, t, G.tfirst);
   const uint64_t A = G.base + G.addr[s], n = G.len[s], tt = t - G.tfirst[s];
   uint64_t lo, hi;
   bscf::tile_range(A, n, tt, &lo, &hi);
@@ -245,7 +237,7 @@ __global__ __launch_bounds__(256) void k_assemble(Pieces Q, uint64_t total, uint
   const uint64_t x0 = (blockIdx.x * 256ull + threadIdx.x) * 16;
   if (x0 >= total) return;
   const uint64_t x1 = mn(x0 + 16, total);
-  uint64_t p = last_le(Q.dst, Q.P, x0);
+  uint64_t p = last_le(Q.P, x0, Q.dst);
   uint64_t lo = 0, hi = 0;
   for (; p < Q.P && Q.dst[p] < x1; p++) {
     const uint64_t d = Q.dst[p], len = Q.len[p];
@@ -323,27 +315,6 @@ void drop_result(spring_bsc_ctx *ctx) {
   memset(&ctx->info, 0, sizeof(ctx->info));
 }
 
-struct Lap {
-  hipEvent_t a = nullptr, b = nullptr;
-  int pass = 0;
-};
-
-struct Laps {
-  RunOwned own;
-  std::vector<Lap> laps;
-  hipStream_t st;
-  hipError_t begin(int pass) {
-    Lap L;
-    L.pass = pass;
-    hipError_t e = own.event(&L.a);
-    if (e == hipSuccess) e = own.event(&L.b);
-    if (e == hipSuccess) e = hipEventRecord(L.a, st);
-    laps.push_back(L);
-    return e;
-  }
-  hipError_t end() { return hipEventRecord(laps.back().b, st); }
-};
-
 // Adler-32 of S segments: addr / len on the host when the tiles can be counted there (d_tfirst == nullptr), else all
 // three arrays are the device's and `bound` is an upper bound of the number of tiles.
 int sum_segments(int dev, hipStream_t st, uint64_t S, uint64_t base, const uint64_t *h_addr, const uint64_t *h_len,
@@ -399,8 +370,7 @@ int frame(spring_bsc_ctx *ctx, spring_bwt_ctx *bwt, spring_qlfc_ctx *qlfc, int f
   const uint64_t P = F + bscf::BLOCK_PIECES * S;
   DBuf d_off, d_src, d_bfile, d_ff, sum_in, sum_body, plen, pdst, psrc, meta, filemeta, kind, block_off, file_off, body_off,
       body_len, body_tiles, body_tfirst, totals, tmp;
-  Laps T;
-  T.st = st;
+  Laps T{st};
   SyncOnExit sync_on_exit{st};
   DALLOC(d_off, (S + 1) * 8); DALLOC(d_src, S * 8); DALLOC(d_bfile, S * 4); DALLOC(d_ff, (F + 1) * 8);
   DALLOC(sum_in, S * 4); DALLOC(sum_body, S * 4);
@@ -471,12 +441,7 @@ int frame(spring_bsc_ctx *ctx, spring_bwt_ctx *bwt, spring_qlfc_ctx *qlfc, int f
   if (S) HIPCHK(rd(st, ctx->block_off.data(), block_off.p, S * 8));
   if (S) HIPCHK(rd(st, ctx->kind.data(), kind.p, S * 4));
   HIPCHK(hipStreamSynchronize(st));
-  for (const Lap &lap : T.laps) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, lap.a, lap.b));
-    I.ms_pass[lap.pass] += ms;
-    I.ms_device += ms;
-  }
+  if ((r = T.collect(I.ms_pass, &I.ms_device))) return r;
   I.bytes_out = total;
   I.coded = h_totals[1 + bscf::CODED];
   I.stored_small = h_totals[1 + bscf::STORED_SMALL];

@@ -23,6 +23,7 @@
 
 #include "bwt_internal.h"
 #include "bwt_plan.h"
+#include "copy_words.h"
 #include "fastq_out_internal.h"
 #include "reorder_device.h"
 #include "reorder_internal.h"
@@ -50,12 +51,7 @@ struct Sub {
 // the segment (relative to G.first) that holds position p < G.m: the last one that starts at or before p, which skips
 // the empty ones
 __device__ __forceinline__ uint32_t seg_of(const Sub &G, uint32_t p) {
-  uint32_t lo = 0, hi = G.count - 1;
-  for (int it = 0; it < 32 && lo < hi; it++) {
-    const uint32_t mid = lo + (hi - lo + 1) / 2;
-    if (G.off[G.first + mid] - G.base <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  return last_le(G.count, p, [&](uint32_t i) { return G.off[G.first + i] - G.base; });
 }
 
 // ------------------------------------------------------------------ first keys
@@ -428,12 +424,8 @@ int transform(spring_bwt_ctx *ctx, const std::vector<uint64_t> &src, spring_bwt_
   DBuf d_off, d_src;
   DALLOC(d_off, (S + 1) * 8);
   DALLOC(d_src, S * 8);
-  uint64_t budget = ctx->workspace_bytes;
-  if (!budget) {
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    budget = free_b > (SORT_FIXED_BYTES << 2) ? (uint64_t)((free_b - (SORT_FIXED_BYTES << 2)) / 10 * 8) : 0;
-  }
+  uint64_t budget = 0;
+  if (int r = workspace_budget(ctx->workspace_bytes, SORT_FIXED_BYTES << 2, &budget)) return r;
   I.workspace_bytes = budget;
   std::vector<uint64_t> first(S + 2);
   const bool runs = ctx->run_keys;

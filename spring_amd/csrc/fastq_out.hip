@@ -6,12 +6,10 @@
 //   length of its id, the offset of the byte modify_id changes, the size of its record  ->  exclusive scan of the sizes
 //   (rec_off[])  ->  the record of every 4 KiB of output  ->  the copy.
 //
-// The copy is destination-driven, as the one of qualid.hip: a lane owns one 16-byte-aligned word of the text, finds the
-// record that covers its first byte in the block's record offsets (LDS), walks the segments id '\n' read '\n' "+\n"
-// quality '\n' of every record that overlaps the word, assembles the bytes of a source segment from one or two aligned
-// 16-byte loads shifted across the source misalignment, and issues one 16-byte store.  The three sources are addressed
-// by absolute byte indices from 16-byte-aligned bases; a 16-byte load that would reach past the end of a source is
-// replaced by byte loads of what exists (the decode context's bases have no padding behind them).
+// The copy is the destination-driven copy of copy_words.h with the records as its pieces: a lane owns one
+// 16-byte-aligned word of the text and walks the segments id '\n' read '\n' "+\n" quality '\n' of every record that
+// overlaps the word.  The three sources are addressed by absolute byte indices from 16-byte-aligned bases, each with
+// the limit behind which nothing is read (the decode context's bases have no padding behind them).
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -24,6 +22,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "copy_words.h"
 #include "fastq_out_internal.h"
 #include "reorder_device.h"
 #include "reorder_internal.h"
@@ -33,8 +32,6 @@
 using namespace sr;
 
 namespace {
-
-typedef unsigned __int128 u128;
 
 // error bits of the device checks
 constexpr uint32_t ERR_OFF = 1, ERR_LONG = 2, ERR_IDNL = 4, ERR_QTAB = 8, ERR_ITAB = 16, ERR_ID1 = 32, ERR_ID3 = 64;
@@ -46,8 +43,6 @@ const char *const ERR_TEXT[7] = {"the read offsets do not start at 0 or decrease
                                  "paired id code 1 on an empty id",
                                  "paired id code 3 on an id without a space, or with its first space at the end"};
 constexpr uint64_t MAX_LINE = 1ull << 30;
-constexpr int COPY_BLOCK_BYTES = 4096;   // 256 lanes x 16 bytes
-constexpr int LDS_RECS = 1024;           // record offsets of a copy block held in LDS (more: searched in memory)
 constexpr uint32_t NO_PATCH = 0xffffffffu;
 constexpr int NUMBERED_MAX = 13;         // '@' + 10 digits + '/' + mate
 
@@ -145,40 +140,6 @@ __global__ void k_tables(const uint64_t *__restrict__ qtab, const uint64_t *__re
 }
 
 // ------------------------------------------------------------------ the copy
-__device__ __forceinline__ u128 ld16(const uint8_t *__restrict__ t, uint64_t a0, uint64_t limit) {   // a0 % 16 == 0
-  if (a0 + 16 <= limit) {
-    const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(t + a0);
-    return ((u128)v.y << 64) | v.x;
-  }
-  u128 v = 0;   // the last word of a source: only the bytes that exist
-  for (uint32_t i = 0; i < 16 && a0 + i < limit; i++) v |= (u128)t[a0 + i] << (8 * i);
-  return v;
-}
-// the c (1..16) bytes from t + a on, in the low bytes of the result, zero above them
-__device__ __forceinline__ u128 fetch(const uint8_t *__restrict__ t, uint64_t a, uint32_t c, uint64_t limit) {
-  const uint64_t a0 = a & ~15ull;
-  const uint32_t sh = (uint32_t)(a & 15);
-  u128 v = ld16(t, a0, limit) >> (8 * sh);
-  if (sh + c > 16) v |= ld16(t, a0 + 16, limit) << (128 - 8 * sh);   // sh > 0 here
-  if (c < 16) v &= ((u128)1 << (8 * c)) - 1;
-  return v;
-}
-
-// largest r in [lo, hi] with off[r] <= p (off[lo] is)
-__device__ __forceinline__ uint64_t find_rec(const uint64_t *__restrict__ off, uint64_t p, uint64_t lo, uint64_t hi) {
-  while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo + 1) / 2;
-    if (off[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-// bs[b] = the record that holds output byte b * 4 KiB (the first byte of copy block b), bs[nblk] = n
-__global__ void k_block_recs(const uint64_t *__restrict__ rec_off, uint64_t n, uint64_t nblk, uint32_t *__restrict__ bs) {
-  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b > nblk) return;
-  bs[b] = (uint32_t)(b < nblk ? find_rec(rec_off, b * COPY_BLOCK_BYTES, 0, n) : n);
-}
-
 struct CopyArg {
   Src id, bases, qual;       // id.lo is not used: idstart[] are indices into id.t
   const uint64_t *roff;      // read offsets from the first unit of the range on (n + 1)
@@ -190,32 +151,34 @@ struct CopyArg {
   uint8_t *out;
 };
 
+// k_assemble's own search, the largest r in [lo, hi] with off[r] <= p (off[lo] is): last_le of copy_words.h without the
+// step counter, which costs this kernel 0.04 ms of its 11.7 at 20 M records (profiles/copy_words_before_after.txt).  It
+// ends because hi - lo at least halves with every step.
+template <class I>
+__device__ __forceinline__ I find_rec(const uint64_t *__restrict__ off, uint64_t p, I lo, I hi) {
+  while (lo < hi) {
+    const I mid = lo + (hi - lo + 1) / 2;
+    if (off[mid] <= p) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 // out[rec_off[i] ..) = id '\n' read '\n' (Q: '+' '\n' quality '\n') of unit i, for all units of the range.
 template <bool Q>
 __global__ __launch_bounds__(256) void k_assemble(CopyArg A) {
-  __shared__ uint64_t soff[LDS_RECS];
-  // the records this block's 4 KiB of output fall into: their offsets go to LDS, where every lane looks up its own
-  const uint64_t blk0 = (uint64_t)blockIdx.x * COPY_BLOCK_BYTES;
+  __shared__ uint64_t soff[COPY_LDS_OFFSETS];
+  // block_piece of copy_words.h with find_rec as its search: the records this block's 4 KiB of output fall into go to
+  // LDS, where every lane looks up its own; more of them than fit there are searched in memory
   const uint64_t s_lo = A.bs[blockIdx.x], s_hi = A.bs[blockIdx.x + 1];
   const uint64_t cnt = s_hi - s_lo + 1;
-  const bool in_lds = cnt <= LDS_RECS;
+  const bool in_lds = cnt <= COPY_LDS_OFFSETS;
   if (in_lds)
     for (uint32_t t = threadIdx.x; t < cnt; t += 256) soff[t] = A.rec_off[s_lo + t];
   __syncthreads();
-  const uint64_t p = blk0 + (uint64_t)threadIdx.x * 16;
+  const uint64_t p = (uint64_t)blockIdx.x * COPY_BLOCK_BYTES + (uint64_t)threadIdx.x * 16;
   if (p >= A.total) return;
   const uint64_t end = min(p + 16, A.total);
-  uint64_t r;
-  if (in_lds) {   // largest t whose offset is <= p
-    uint32_t lo = 0, hi = (uint32_t)cnt - 1;
-    while (lo < hi) {
-      const uint32_t mid = lo + (hi - lo + 1) / 2;
-      if (soff[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    r = s_lo + lo;
-  } else {
-    r = find_rec(A.rec_off, p, s_lo, s_hi);
-  }
+  uint64_t r = in_lds ? s_lo + find_rec<uint32_t>(soff, p, 0, (uint32_t)cnt - 1) : find_rec<uint64_t>(A.rec_off, p, s_lo, s_hi);
   uint64_t ro = A.rec_off[r], q = p;
   u128 acc = 0;
   while (q < end) {   // a record is at least two bytes: at most eight of them meet a word
@@ -251,13 +214,7 @@ __global__ __launch_bounds__(256) void k_assemble(CopyArg A) {
     ro += size;
     r++;
   }
-  const uint32_t nb = (uint32_t)(end - p);
-  if (nb == 16) {
-    *reinterpret_cast<uint4 *>(A.out + p) =
-        make_uint4((uint32_t)acc, (uint32_t)(acc >> 32), (uint32_t)(acc >> 64), (uint32_t)(acc >> 96));
-  } else {   // the last, partial word of the text
-    for (uint32_t i = 0; i < nb; i++) A.out[p + i] = (uint8_t)(acc >> (8 * i));
-  }
+  put16(A.out, p, (uint32_t)(end - p), acc);
 }
 
 // ------------------------------------------------------------------ host side
@@ -521,7 +478,8 @@ int assemble(spring_fastq_out_ctx *ctx, const spring_fastq_out_params &P, const 
     const dim3 g = grid(total, COPY_BLOCK_BYTES);
     const uint64_t nblk = g.x;
     DALLOC(bs, (nblk + 1) * 4);
-    hipLaunchKernelGGL(k_block_recs, grid(nblk + 1), dim3(256), 0, st, ctx->rec_off.as<uint64_t>(), n, nblk, bs.as<uint32_t>());
+    hipLaunchKernelGGL(k_block_pieces<ArrayKey<uint64_t>>, grid(nblk + 1), dim3(256), 0, st,
+                       ArrayKey<uint64_t>{ctx->rec_off.as<uint64_t>()}, n, nblk, bs.as<uint32_t>());
     CopyArg C;
     C.id = ids; C.bases = bases; C.qual = qual;
     C.roff = roff + r0; C.idstart = idstart.as<uint64_t>(); C.idlen = idlen.as<uint32_t>(); C.patch = patch.as<uint32_t>();

@@ -4,7 +4,7 @@
 //   member cuts  ->  chunk table  ->  match + parse (one wavefront per chunk, hash table in LDS)  ->  histograms, length-
 //   limited codes and the block header (one wavefront per chunk, gzip_codes.h)  ->  emit (token bit lengths, scan, bits
 //   through LDS into the chunk's slot)  ->  CRC-32 per chunk  ->  scan of the chunk sizes  ->  the copy of headers,
-//   chunks and trailers to their final place, one 16-byte word per lane.
+//   chunks and trailers to their final place, one 16-byte word per lane (copy_words.h).
 //
 // Every loop on the device has a static bound; a wrong table entry ends in a wrong byte.
 #include <fcntl.h>
@@ -18,6 +18,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "copy_words.h"
 #include "fastq_out_internal.h"
 #include "gzip_codes.h"
 #include "reorder_device.h"
@@ -28,8 +29,6 @@
 using namespace sr;
 
 namespace {
-
-typedef unsigned __int128 u128;
 
 constexpr uint32_t DEFAULT_CHUNK = 32768;
 constexpr int HASH_BITS = 14;                  // 16384 slots of 16 bits: 32 KiB of LDS per workgroup
@@ -75,11 +74,7 @@ __global__ void k_chunk_table(const uint64_t *__restrict__ moff, const uint64_t 
                               uint64_t NC, uint32_t chunk, Chunks C) {
   const uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= NC) return;
-  uint64_t lo = 0, hi = M - 1;   // the last member whose first chunk is <= c
-  for (int it = 0; it < 64 && lo < hi; it++) {
-    const uint64_t mid = lo + (hi - lo + 1) / 2;
-    if (cfirst[mid] <= c) lo = mid; else hi = mid - 1;
-  }
+  const uint64_t lo = last_le(M, c, cfirst);   // the last member whose first chunk is <= c
   const uint64_t k = c - cfirst[lo], s = moff[lo] + k * chunk, e = min(s + chunk, moff[lo + 1]);
   C.start[c] = s;
   C.len[c] = (uint32_t)(e - s);
@@ -387,25 +382,6 @@ __global__ void k_seg_sizes(Chunks C, uint64_t NC, uint32_t *__restrict__ seg) {
   seg[c] = c < NC ? C.payload[c] + ((C.flags[c] & F_FIRST) ? 10 : 0) + ((C.flags[c] & F_LAST) ? 8 : 0) : 0;
 }
 
-__device__ __forceinline__ u128 ld16(const uint8_t *__restrict__ t, uint64_t a0, uint64_t limit) {   // a0 % 16 == 0
-  if (a0 + 16 <= limit) {
-    const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(t + a0);
-    return ((u128)v.y << 64) | v.x;
-  }
-  u128 v = 0;   // the last word of a source: only the bytes that exist
-  for (uint32_t i = 0; i < 16 && a0 + i < limit; i++) v |= (u128)t[a0 + i] << (8 * i);
-  return v;
-}
-// the c (1..16) bytes from t + a on, in the low bytes of the result, zero above them
-__device__ __forceinline__ u128 fetch(const uint8_t *__restrict__ t, uint64_t a, uint32_t c, uint64_t limit) {
-  const uint64_t a0 = a & ~15ull;
-  const uint32_t sh = (uint32_t)(a & 15);
-  u128 v = ld16(t, a0, limit) >> (8 * sh);
-  if (sh + c > 16) v |= ld16(t, a0 + 16, limit) << (128 - 8 * sh);   // sh > 0 here
-  if (c < 16) v &= ((u128)1 << (8 * c)) - 1;
-  return v;
-}
-
 struct CompactArg {
   const uint8_t *t;            // the source, t[0, limit) exists
   uint64_t limit;
@@ -423,12 +399,7 @@ __global__ __launch_bounds__(256) void k_compact(CompactArg A) {
   const uint64_t p = ((uint64_t)blockIdx.x * 256 + threadIdx.x) * 16;
   if (p >= A.total) return;
   const uint64_t end = min(p + 16, A.total);
-  uint64_t lo = 0, hi = A.NC - 1;
-  for (int it = 0; it < 64 && lo < hi; it++) {
-    const uint64_t mid = lo + (hi - lo + 1) / 2;
-    if (A.out_off[mid] <= p) lo = mid; else hi = mid - 1;
-  }
-  uint64_t c = lo, q = p;
+  uint64_t c = last_le(A.NC, p, A.out_off), q = p;
   u128 acc = 0;
   for (int guard = 0; guard < 16 && q < end; guard++) {   // a segment is at least 6 bytes
     const uint64_t so = A.out_off[c];
@@ -467,13 +438,7 @@ __global__ __launch_bounds__(256) void k_compact(CompactArg A) {
     }
     c++;
   }
-  const uint32_t nb = (uint32_t)(end - p);
-  if (nb == 16) {
-    *reinterpret_cast<uint4 *>(A.out + p) =
-        make_uint4((uint32_t)acc, (uint32_t)(acc >> 32), (uint32_t)(acc >> 64), (uint32_t)(acc >> 96));
-  } else {   // the last, partial word
-    for (uint32_t i = 0; i < nb; i++) A.out[p + i] = (uint8_t)(acc >> (8 * i));
-  }
+  put16(A.out, p, (uint32_t)(end - p), acc);
 }
 
 // ------------------------------------------------------------------ host side

@@ -505,12 +505,8 @@ int run(spring_idcodec_ctx *ctx, const uint8_t *d_lines, uint64_t nbytes, const 
   HIPCHK(hipMemcpyAsync(d_cap.p, cap.data(), (nb + 1) * 8, hipMemcpyHostToDevice, st));
   HIPCHK(hipMemsetAsync(flag.p, 0, 4, st));
   const uint64_t per_block = workspace_need(1, I.max_tokens);
-  uint64_t budget = ctx->workspace_bytes;
-  if (!budget) {
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    budget = (uint64_t)free_b / 10 * 8;
-  }
+  uint64_t budget = 0;
+  if (int r = workspace_budget(ctx->workspace_bytes, 0, &budget)) return r;
   const uint64_t per_sub = std::min<uint64_t>(nb, budget / per_block);
   if (per_sub == 0)
     return fail(SPRING_REORDER_E_ARG, "the models of one block (%llu tokens an id) need %llu bytes of workspace, the budget is %llu",

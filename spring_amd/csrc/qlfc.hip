@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bwt_internal.h"
+#include "copy_words.h"
 #include "qlfc_plan.h"
 #include "reorder_device.h"
 #include "reorder_internal.h"
@@ -62,16 +63,6 @@ struct Chunks {
   uint32_t *start;   // C + 1: first position; start[C] = m
   uint32_t *run;     // C + 1: first run; run[C] = R
 };
-
-// the last entry of a[0 .. n) that is <= x (a[0] <= x, a ascending)
-__device__ __forceinline__ uint32_t last_le(const uint32_t *a, uint32_t n, uint32_t x) {
-  uint32_t lo = 0, hi = n - 1;
-  for (int it = 0; it < 32 && lo < hi; it++) {
-    const uint32_t mid = lo + (hi - lo + 1) / 2;
-    if (a[mid] <= x) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 __device__ __forceinline__ const uint8_t *byte_at(const Sub &G, const Chunks &K, uint32_t c, uint32_t p) {
   const uint32_t s = K.seg[c];
@@ -127,7 +118,7 @@ __global__ __launch_bounds__(1024) void k_cuts(Sub G, Chunks K) {
 __global__ __launch_bounds__(256) void k_heads(Sub G, Chunks K, uint32_t *__restrict__ flag) {
   const uint32_t p = blockIdx.x * 256u + threadIdx.x;
   if (p >= G.m) return;
-  const uint32_t c = last_le(K.start, G.C, p);
+  const uint32_t c = last_le(G.C, p, K.start);
   bool head = p == K.start[c];
   if (!head) {
     const uint8_t *a = byte_at(G, K, c, p);
@@ -148,7 +139,7 @@ __global__ __launch_bounds__(256) void k_runs(Sub G, Chunks K, const uint32_t *_
     counter[0] = R;
   }
   if (!flag[p]) return;
-  const uint32_t r = ridx[p], c = last_le(K.start, G.C, p);
+  const uint32_t r = ridx[p], c = last_le(G.C, p, K.start);
   rpos[r] = p;
   rsym[r] = *byte_at(G, K, c, p);
   if (p == K.start[c]) K.run[c] = r;
@@ -186,14 +177,14 @@ __global__ __launch_bounds__(64) void k_ranks(Chunks K, uint32_t C, const uint8_
   const uint32_t t = blockIdx.x, l = threadIdx.x;
   uint32_t nx[4], sym[4], chunk[4];
   const uint32_t rl = min(R, (t + 1) * TILE) - 1;   // the tile's last run
-  const uint32_t cl = last_le(K.run, C, rl), end = K.run[cl + 1];
+  const uint32_t cl = last_le(C, rl, K.run), end = K.run[cl + 1];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     const uint32_t v = next[t * TILE + k * 64 + l];
     nx[k] = v < end ? v : INF;
     const uint32_t r = t * TILE + k * 64 + l;
     sym[k] = r < R ? rsym[r] : 0;
-    chunk[k] = r < R ? last_le(K.run, C, r) : 0;
+    chunk[k] = r < R ? last_le(C, r, K.run) : 0;
   }
 #pragma unroll
   for (int k = 3; k >= 0; k--) {
@@ -316,7 +307,7 @@ __global__ __launch_bounds__(256) void k_events(Chunks K, uint32_t C, uint32_t R
                                                 uint32_t *__restrict__ lastev) {
   const uint32_t r = blockIdx.x * 256u + threadIdx.x;
   if (r >= R) return;
-  const uint32_t ch = last_le(K.run, C, r);
+  const uint32_t ch = last_le(C, r, K.run);
   const int maxrank = qlfc::max_rank(nsym[ch]);
   const uint32_t sym = rsym[r], rank = rrank[r], run = rpos[r + 1] - rpos[r];
   uint32_t e = cev[ch] + evoff[r];
@@ -522,11 +513,6 @@ void drop_result(spring_qlfc_ctx *ctx) {
   memset(&ctx->info, 0, sizeof(ctx->info));
 }
 
-struct Lap {   // one timed span on the stream; ms is read after a synchronisation
-  hipEvent_t a = nullptr, b = nullptr;
-  int pass = 0;
-};
-
 // One sub-batch, segments [first, first + count).  *fit = false: its events do not fit the budget (nothing is kept).
 int code_sub(spring_qlfc_ctx *ctx, const uint64_t *off, const uint64_t *d_src, const uint64_t *d_off, const uint64_t *h_src,
              uint64_t first, uint64_t count, uint64_t budget, bool *fit, uint64_t *events_need) {
@@ -559,18 +545,7 @@ int code_sub(spring_qlfc_ctx *ctx, const uint64_t *off, const uint64_t *d_src, c
     keep(new DBuf(), 0);
     return 0;
   }
-  RunOwned own;
-  std::vector<Lap> laps;
-  auto lap_begin = [&](int pass) -> hipError_t {
-    Lap L;
-    L.pass = pass;
-    hipError_t e = own.event(&L.a);
-    if (e == hipSuccess) e = own.event(&L.b);
-    if (e == hipSuccess) e = hipEventRecord(L.a, st);
-    laps.push_back(L);
-    return e;
-  };
-  auto lap_end = [&]() { return hipEventRecord(laps.back().b, st); };
+  Laps T{st};
   DBuf d_cfirst, cseg, cstart, crun, flag, ridx, rpos, rsym, rrank, irank, irun, resc, evoff, tiles, order, nsym, cevn, cev,
       lastev, counter, tmp, pay, payoff, clen, poslast;
   SyncOnExit sync_on_exit{st};
@@ -589,7 +564,7 @@ int code_sub(spring_qlfc_ctx *ctx, const uint64_t *off, const uint64_t *d_src, c
   Sub G{d_src, d_off, d_cfirst.as<uint32_t>(), (uint32_t)first, (uint32_t)count, off[first], m, C};
   Chunks K{cseg.as<uint32_t>(), cstart.as<uint32_t>(), crun.as<uint32_t>()};
   // ---- 1: cuts, runs, ranks
-  HIPCHK(lap_begin(0));
+  HIPCHK(T.begin(0));
   hipLaunchKernelGGL(k_cuts, dim3((unsigned)count), dim3(1024), 0, st, G, K);
   hipLaunchKernelGGL(k_heads, grid(m), dim3(256), 0, st, G, K, flag.as<uint32_t>());
   HIPCHK(sr::excl_scan_u32(st, tmp.p, scan_bytes, flag.as<uint32_t>(), ridx.as<uint32_t>(), m));
@@ -605,13 +580,13 @@ int code_sub(spring_qlfc_ctx *ctx, const uint64_t *off, const uint64_t *d_src, c
   hipLaunchKernelGGL(k_tile_next, dim3(1), dim3(256), 0, st, tiles.as<uint32_t>(), ntiles);
   hipLaunchKernelGGL(k_ranks, dim3(ntiles), dim3(64), 0, st, K, C, rsym.as<uint8_t>(), R, tiles.as<uint32_t>(), rrank.as<uint8_t>(),
                      order.as<uint8_t>(), nsym.as<uint32_t>());
-  HIPCHK(lap_end());
+  HIPCHK(T.end());
   // ---- 2: contexts, then the events once their number is known
-  HIPCHK(lap_begin(1));
+  HIPCHK(T.begin(1));
   hipLaunchKernelGGL(k_contexts, dim3(C), dim3(64), 0, st, K, rsym.as<uint8_t>(), rrank.as<uint8_t>(), rpos.as<uint32_t>(),
                      nsym.as<uint32_t>(), irank.as<uint16_t>(), irun.as<uint16_t>(), resc.as<uint8_t>(), evoff.as<uint32_t>(),
                      cevn.as<uint64_t>());
-  HIPCHK(lap_end());
+  HIPCHK(T.end());
   HIPCHK(hipGetLastError());
   std::vector<uint64_t> h_cevn(C);
   std::vector<uint32_t> h_cstart(C + 1), h_cev(C + 1, 0);
@@ -639,14 +614,14 @@ int code_sub(spring_qlfc_ctx *ctx, const uint64_t *off, const uint64_t *d_src, c
   DALLOC(key, 3 * E * 8); DALLOC(key2, 3 * E * 8); DALLOC(val, 3 * E * 4); DALLOC(val2, 3 * E * 4);
   DALLOC(ebit, E); DALLOC(pval, 3 * E * 2); DALLOC(prob, E * 4); DALLOC(sort_tmp, sort_bytes + 16);
   EventOut V{key.as<uint64_t>(), val.as<uint32_t>(), ebit.as<uint8_t>()};
-  HIPCHK(lap_begin(1));
+  HIPCHK(T.begin(1));
   hipLaunchKernelGGL(k_events, grid(R), dim3(256), 0, st, K, C, R, rsym.as<uint8_t>(), rrank.as<uint8_t>(), rpos.as<uint32_t>(),
                      nsym.as<uint32_t>(), irank.as<uint16_t>(), irun.as<uint16_t>(), ctx->rank_tab.as<uint8_t>(), ctx->run_tab.as<uint8_t>(),
                      resc.as<uint8_t>(), evoff.as<uint32_t>(),
                      cev.as<uint32_t>(), V, lastev.as<uint32_t>());
-  HIPCHK(lap_end());
+  HIPCHK(T.end());
   // ---- 3: slots
-  HIPCHK(lap_begin(2));
+  HIPCHK(T.begin(2));
   int cbits = 1;
   while ((1ull << cbits) < C) cbits++;
   size_t sb = sort_bytes;
@@ -654,17 +629,17 @@ int code_sub(spring_qlfc_ctx *ctx, const uint64_t *off, const uint64_t *d_src, c
                         (unsigned)(qlfc::SLOT_BITS + cbits)));
   hipLaunchKernelGGL(k_chains, grid(3 * E), dim3(256), 0, st, key2.as<uint64_t>(), val2.as<uint32_t>(), ebit.as<uint8_t>(),
                      (uint32_t)(3 * E), pval.as<int16_t>());
-  HIPCHK(lap_end());
+  HIPCHK(T.end());
   // ---- 4: probabilities
-  HIPCHK(lap_begin(3));
+  HIPCHK(T.begin(3));
   hipLaunchKernelGGL(k_probs, grid(E), dim3(256), 0, st, ebit.as<uint8_t>(), pval.as<int16_t>(), (uint32_t)E, prob.as<int32_t>());
-  HIPCHK(lap_end());
+  HIPCHK(T.end());
   // ---- 5: range coder
-  HIPCHK(lap_begin(4));
+  HIPCHK(T.begin(4));
   hipLaunchKernelGGL(k_coder, dim3(C), dim3(64), 0, st, K, order.as<uint8_t>(), nsym.as<uint32_t>(), cev.as<uint32_t>(),
                      lastev.as<uint32_t>(), ebit.as<uint8_t>(), prob.as<int32_t>(), pay.as<uint8_t>(), payoff.as<uint64_t>(),
                      clen.as<uint32_t>(), poslast.as<uint32_t>());
-  HIPCHK(lap_end());
+  HIPCHK(T.end());
   HIPCHK(hipGetLastError());
   std::vector<uint32_t> h_clen(C), h_poslast(C);
   HIPCHK(rd(st, h_clen.data(), clen.p, (size_t)C * 4));
@@ -739,19 +714,14 @@ int code_sub(spring_qlfc_ctx *ctx, const uint64_t *off, const uint64_t *d_src, c
     for (size_t i : head_piece) pieces[i].src += (uint64_t)(uintptr_t)d_heads.p;
     HIPCHK(hipMemcpyAsync(d_heads.p, heads.data(), heads.size(), hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_pieces.p, pieces.data(), pieces.size() * sizeof(Piece), hipMemcpyHostToDevice, st));
-    HIPCHK(lap_begin(5));
+    HIPCHK(T.begin(5));
     hipLaunchKernelGGL(k_assemble, dim3((unsigned)pieces.size()), dim3(256), 0, st, d_pieces.as<Piece>(), out->as<uint8_t>());
-    HIPCHK(lap_end());
+    HIPCHK(T.end());
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));   // heads and pieces are read until here
   }
   HIPCHK(hipStreamSynchronize(st));
-  for (const Lap &L : laps) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, L.a, L.b));
-    I.ms_pass[L.pass] += ms;
-    I.ms_device += ms;
-  }
+  if (int r = T.collect(I.ms_pass, &I.ms_device)) return r;
   I.chunks += C;
   I.runs += R;
   I.events += E;
@@ -774,12 +744,8 @@ int code_batch(spring_qlfc_ctx *ctx, const std::vector<uint64_t> &off, const std
   DBuf d_off, d_src;
   DALLOC(d_off, (S + 1) * 8);
   DALLOC(d_src, S * 8);
-  uint64_t budget = ctx->workspace_bytes;
-  if (!budget) {
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    budget = (uint64_t)(free_b / 10 * 8);
-  }
+  uint64_t budget = 0;
+  if (int r = workspace_budget(ctx->workspace_bytes, 0, &budget)) return r;
   I.workspace_bytes = budget;
   SyncOnExit sync_on_exit{st};
   HIPCHK(hipMemcpyAsync(d_off.p, off.data(), (S + 1) * 8, hipMemcpyHostToDevice, st));

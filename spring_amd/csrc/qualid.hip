@@ -6,16 +6,16 @@
 //   through the inverse of order_array  ->  exclusive scan of the lengths (off[]; block b starts at off[b * B])
 //   ->  the slot of every 4 KiB of output  ->  the copy.
 //
-// The copy is destination-driven: a lane owns one 16-byte-aligned word of the output, finds the slot(s) that cover it
-// by a search in off[], assembles the source bytes from aligned 16-byte loads (byte-aligned across the source
-// misalignment, walking over as many lines as the word spans), applies the quantization table from LDS and issues one
-// 16-byte store.  Id lines get their '\n' from the kernel: with NL = 1 slot s starts at off[s] + s.
+// The copy is the destination-driven copy of copy_words.h with the slots as its pieces: a lane owns one 16-byte-aligned
+// word of the output, walks over as many lines as the word spans, applies the quantization table from LDS and stores
+// the word.  Id lines get their '\n' from the kernel: with NL = 1 slot s starts at off[s] + s.
 #include <algorithm>
 #include <cstring>
 #include <vector>
 
 #include <hip/hip_runtime.h>
 
+#include "copy_words.h"
 #include "encoder_internal.h"
 #include "fastq_out_internal.h"
 #include "reorder_device.h"
@@ -27,12 +27,8 @@ using namespace sr;
 
 namespace {
 
-typedef unsigned __int128 u128;
-
 // error bits of the device checks
 constexpr uint32_t ERR_PERM = 1, ERR_QLEN = 2, ERR_LONG = 4, ERR_BYTE = 8;
-constexpr int COPY_BLOCK_BYTES = 4096;   // 256 lanes x 16 bytes
-constexpr int LDS_SLOTS = 1024;          // slot offsets of a copy block held in LDS (more: searched in memory)
 constexpr int CHANGED_SLOTS = 1024;      // counters the copy's blocks spread their bytes_changed over
 
 // ------------------------------------------------------------------ order -> the line of every slot
@@ -99,40 +95,12 @@ __global__ void k_lines_plain(const uint64_t *__restrict__ line_end, uint64_t U,
 }
 
 // ------------------------------------------------------------------ the copy
-__device__ __forceinline__ u128 ld16(const uint8_t *__restrict__ p) {   // p 16-byte aligned
-  const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(p);
-  return ((u128)v.y << 64) | v.x;
-}
-// the c (1..16) bytes from txt + a on, in the low bytes of the result (bytes above them unspecified)
-__device__ __forceinline__ u128 fetch(const uint8_t *__restrict__ txt, uint64_t a, uint32_t c) {
-  const uint64_t a0 = a & ~15ull;
-  const uint32_t sh = (uint32_t)(a & 15);
-  u128 v = ld16(txt + a0) >> (8 * sh);
-  if (sh + c > 16) v |= ld16(txt + a0 + 16) << (128 - 8 * sh);   // sh > 0 here
-  return v;
-}
-
+// the offset of slot s in the output: the key of the copy's searches (copy_words.h)
 template <int NL>
 struct Offs {
   const uint64_t *__restrict__ off;
   __device__ __forceinline__ uint64_t operator()(uint64_t s) const { return off[s] + (NL ? s : 0); }
-  // largest s in [lo, hi] whose offset is <= p (the offset of lo is)
-  __device__ __forceinline__ uint64_t find(uint64_t p, uint64_t lo, uint64_t hi) const {
-    while (lo < hi) {
-      const uint64_t mid = lo + (hi - lo + 1) / 2;
-      if ((*this)(mid) <= p) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-  }
 };
-
-// bs[b] = the slot that holds output byte b * 4 KiB (the first byte of copy block b), bs[nblk] = U
-template <int NL>
-__global__ void k_block_slots(const uint64_t *__restrict__ off, uint64_t U, uint64_t nblk, uint32_t *__restrict__ bs) {
-  const uint64_t b = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b > nblk) return;
-  bs[b] = (uint32_t)(b < nblk ? Offs<NL>{off}.find(b * COPY_BLOCK_BYTES, 0, U) : U);
-}
 
 // out[off[s] + NL * s ..) = line of slot s (+ '\n' when NL), for all slots; total = off[U] + NL * U bytes.
 // TAB: every byte b becomes table[b] (b < 128; else ERR_BYTE); changed[CHANGED_SLOTS] together count the bytes that
@@ -144,33 +112,15 @@ __global__ __launch_bounds__(256) void k_copy_words(const uint8_t *__restrict__ 
                                                     const uint8_t *__restrict__ table, uint8_t *__restrict__ out,
                                                     unsigned long long *__restrict__ changed, uint32_t *__restrict__ err) {
   __shared__ uint8_t tab[128];
-  __shared__ uint64_t soff[LDS_SLOTS];
+  __shared__ uint64_t soff[COPY_LDS_OFFSETS];
   __shared__ uint32_t wave_changed[4];
   if (TAB && threadIdx.x < 128) tab[threadIdx.x] = table[threadIdx.x];
   const Offs<NL> eoff{off};
-  // the slots this block's 4 KiB of output fall into: their offsets go to LDS, where every lane looks up its own
-  const uint64_t blk0 = (uint64_t)blockIdx.x * COPY_BLOCK_BYTES;
-  const uint64_t s_lo = bs[blockIdx.x], s_hi = bs[blockIdx.x + 1];
-  const uint64_t cnt = s_hi - s_lo + 1;
-  const bool in_lds = cnt <= LDS_SLOTS;
-  if (in_lds)
-    for (uint32_t t = threadIdx.x; t < cnt; t += 256) soff[t] = eoff(s_lo + t);
-  __syncthreads();
-  const uint64_t p = blk0 + (uint64_t)threadIdx.x * 16;
+  const uint64_t p = (uint64_t)blockIdx.x * COPY_BLOCK_BYTES + (uint64_t)threadIdx.x * 16;
+  uint64_t s = block_piece(eoff, bs, p, p < total, soff);   // synchronises: tab is there as well
   uint32_t nchanged = 0;
   if (p < total) {
     const uint64_t end = min(p + 16, total);
-    uint64_t s;
-    if (in_lds) {   // largest t whose offset is <= p
-      uint32_t lo = 0, hi = (uint32_t)cnt - 1;
-      while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (soff[mid] <= p) lo = mid; else hi = mid - 1;
-      }
-      s = s_lo + lo;
-    } else {
-      s = eoff.find(p, s_lo, s_hi);
-    }
     uint64_t so = eoff(s), q = p;
     u128 acc = 0;
     while (q < end) {
@@ -178,9 +128,7 @@ __global__ __launch_bounds__(256) void k_copy_words(const uint8_t *__restrict__ 
       const uint64_t k = q - so;
       if (k < l) {
         const uint32_t c = (uint32_t)min((uint64_t)l - k, end - q);
-        u128 v = fetch(txt, start[s] + k, c);
-        if (c < 16) v &= ((u128)1 << (8 * c)) - 1;
-        acc |= v << (8 * (uint32_t)(q - p));
+        acc |= fetch(txt, start[s] + k, c, ~0ull) << (8 * (uint32_t)(q - p));   // txt is padded: no last word
         q += c;
       } else if (NL && k == l) {
         acc |= (u128)'\n' << (8 * (uint32_t)(q - p));
@@ -189,8 +137,8 @@ __global__ __launch_bounds__(256) void k_copy_words(const uint8_t *__restrict__ 
       if (q >= so + l + NL) { so += (uint64_t)l + NL; s++; }   // on to the next slot (it may be empty)
     }
     const uint32_t nb = (uint32_t)(end - p);
-    uint32_t w[4] = {(uint32_t)acc, (uint32_t)(acc >> 32), (uint32_t)(acc >> 64), (uint32_t)(acc >> 96)};
     if (TAB) {
+      uint32_t w[4] = {(uint32_t)acc, (uint32_t)(acc >> 32), (uint32_t)(acc >> 64), (uint32_t)(acc >> 96)};
       uint32_t bad = 0;
 #pragma unroll
       for (int i = 0; i < 4; i++) {
@@ -206,12 +154,9 @@ __global__ __launch_bounds__(256) void k_copy_words(const uint8_t *__restrict__ 
         w[i] = r;
       }
       if (bad) atomicOr(err, ERR_BYTE);
+      acc = (u128)w[3] << 96 | (u128)w[2] << 64 | (u128)w[1] << 32 | w[0];
     }
-    if (nb == 16) {
-      *reinterpret_cast<uint4 *>(out + p) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {   // the last, partial word of the output
-      for (uint32_t i = 0; i < nb; i++) out[p + i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-    }
+    put16(out, p, nb, acc);
   }
   if (TAB) {
 #pragma unroll
@@ -441,8 +386,8 @@ int run_core(spring_qualid_ctx *ctx, const uint8_t *text, size_t nbytes, bool fa
       const dim3 g = grid(total, COPY_BLOCK_BYTES);
       const uint64_t nblk = g.x;
       DALLOC(K[k].bs, (nblk + 1) * 4);
-      if (nl) hipLaunchKernelGGL(k_block_slots<1>, grid(nblk + 1), dim3(256), 0, st, K[k].off.as<uint64_t>(), U, nblk, K[k].bs.as<uint32_t>());
-      else hipLaunchKernelGGL(k_block_slots<0>, grid(nblk + 1), dim3(256), 0, st, K[k].off.as<uint64_t>(), U, nblk, K[k].bs.as<uint32_t>());
+      if (nl) hipLaunchKernelGGL(k_block_pieces<Offs<1>>, grid(nblk + 1), dim3(256), 0, st, Offs<1>{K[k].off.as<uint64_t>()}, U, nblk, K[k].bs.as<uint32_t>());
+      else hipLaunchKernelGGL(k_block_pieces<Offs<0>>, grid(nblk + 1), dim3(256), 0, st, Offs<0>{K[k].off.as<uint64_t>()}, U, nblk, K[k].bs.as<uint32_t>());
 #define COPY(NLV, TABV)                                                                                          \
   hipLaunchKernelGGL((k_copy_words<NLV, TABV>), g, dim3(256), 0, st, T.txt.as<uint8_t>(), K[k].start.as<uint64_t>(), \
                      ctx->len[k].as<uint32_t>(), K[k].off.as<uint64_t>(), K[k].bs.as<uint32_t>(), total, d_table.as<uint8_t>(), \

@@ -81,6 +81,52 @@ struct RunOwned {
   }
 };
 
+// Timed spans on one stream, each counted towards a pass of the stage's info.  The events live as long as the holder:
+// declare it in front of the function's SyncOnExit, so that no span is in flight when they are destroyed.
+struct Lap {
+  hipEvent_t a = nullptr, b = nullptr;
+  int pass = 0;
+};
+struct Laps {
+  hipStream_t st;
+  RunOwned own;
+  std::vector<Lap> laps;
+  explicit Laps(hipStream_t s) : st(s) {}
+  hipError_t begin(int pass) {
+    Lap L;
+    L.pass = pass;
+    hipError_t e = own.event(&L.a);
+    if (e == hipSuccess) e = own.event(&L.b);
+    if (e == hipSuccess) e = hipEventRecord(L.a, st);
+    laps.push_back(L);
+    return e;
+  }
+  hipError_t end() { return hipEventRecord(laps.back().b, st); }
+  // After a synchronisation of the stream: every span's time is added to ms_pass[its pass] and to *ms_device.  A HIP
+  // failure is reported with this header's file and line, not the stage's (HIPCHK sits here).
+  int collect(double *ms_pass, double *ms_device) const {
+    for (const Lap &L : laps) {
+      float ms = 0;
+      HIPCHK(hipEventElapsedTime(&ms, L.a, L.b));
+      ms_pass[L.pass] += ms;
+      *ms_device += ms;
+    }
+    return 0;
+  }
+};
+
+// The workspace a stage may take: what the caller set on the context (ctx_bytes != 0), else eight tenths of the free
+// device memory beyond hold_back (0 when less than that is free).  A failure of hipMemGetInfo is reported with this
+// header's file and line.
+inline int workspace_budget(uint64_t ctx_bytes, uint64_t hold_back, uint64_t *budget) {
+  *budget = ctx_bytes;
+  if (ctx_bytes) return 0;
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  *budget = free_b > hold_back ? (uint64_t)((free_b - hold_back) / 10 * 8) : 0;
+  return 0;
+}
+
 // Declare it behind the buffers of a function: whatever is in flight ends before they go back to the pool.
 struct SyncOnExit {
   hipStream_t st;

@@ -20,6 +20,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "bwt_internal.h"
+#include "copy_words.h"
 #include "reorder_internal.h"
 #include "spring_unbwt.h"
 #include "stage_host.h"
@@ -64,21 +65,11 @@ __device__ __forceinline__ Seg seg_at(const Sub &G, uint32_t s) {
 
 // the segment that holds byte p < G.m: the last one that starts at or before p, which skips the empty ones
 __device__ __forceinline__ uint32_t seg_of_byte(const Sub &G, uint32_t p) {
-  uint32_t lo = 0, hi = G.count - 1;
-  for (int it = 0; it < 32 && lo < hi; it++) {
-    const uint32_t mid = lo + (hi - lo + 1) / 2;
-    if (G.off[G.first + mid] - G.base <= p) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  return last_le(G.count, p, [&](uint32_t i) { return G.off[G.first + i] - G.base; });
 }
 // the segment that owns row r < G.rows: every segment has at least one row, so the row starts strictly increase
 __device__ __forceinline__ uint32_t seg_of_row(const Sub &G, uint32_t r) {
-  uint32_t lo = 0, hi = G.count - 1;
-  for (int it = 0; it < 32 && lo < hi; it++) {
-    const uint32_t mid = lo + (hi - lo + 1) / 2;
-    if (G.off[G.first + mid] - G.base + mid <= r) lo = mid; else hi = mid - 1;
-  }
-  return lo;
+  return last_le(G.count, r, [&](uint32_t i) { return G.off[G.first + i] - G.base + i; });
 }
 
 // ------------------------------------------------------------------ rows and keys
@@ -384,12 +375,8 @@ int invert(spring_unbwt_ctx *ctx, const std::vector<uint64_t> &src, const int32_
   DBuf d_off, d_src;
   DALLOC(d_off, (S + 1) * 8);
   DALLOC(d_src, S * 8);
-  uint64_t budget = ctx->workspace_bytes;
-  if (!budget) {
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    budget = free_b > (SORT_FIXED_BYTES << 2) ? (uint64_t)((free_b - (SORT_FIXED_BYTES << 2)) / 10 * 8) : 0;
-  }
+  uint64_t budget = 0;
+  if (int r = workspace_budget(ctx->workspace_bytes, SORT_FIXED_BYTES << 2, &budget)) return r;
   I.workspace_bytes = budget;
   std::vector<uint64_t> first(S + 2);
   const int64_t nsub = unbwt::plan_sub_batches(off.data(), S, budget, first.data());

@@ -350,11 +350,6 @@ void drop_result(spring_unqlfc_ctx *ctx) {
   memset(&ctx->info, 0, sizeof(ctx->info));
 }
 
-struct Lap {   // one timed span on the stream; ms is read after a synchronisation
-  hipEvent_t a = nullptr, b = nullptr;
-  int pass = 0;
-};
-
 // The batch: S coded segments at the device addresses src with the offsets coded_off, out_size[s] bytes each decoded.
 int decode_batch(spring_unqlfc_ctx *ctx, const std::vector<uint64_t> &coded_off, const std::vector<uint64_t> &src,
                  const uint64_t *out_size, spring_unqlfc_info *info_out) {
@@ -377,31 +372,16 @@ int decode_batch(spring_unqlfc_ctx *ctx, const std::vector<uint64_t> &coded_off,
   I.bytes_out = off[S];
   DALLOC(ctx->out, I.bytes_out + 16);
   uint8_t *out = ctx->out.as<uint8_t>();
-  uint64_t budget = ctx->workspace_bytes;
-  const bool own_budget = budget != 0;
-  if (!budget) {
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    budget = (uint64_t)(free_b / 10 * 8);
-  }
+  const bool own_budget = ctx->workspace_bytes != 0;
+  uint64_t budget = 0;
+  if (int r = workspace_budget(ctx->workspace_bytes, 0, &budget)) return r;
   I.workspace_bytes = budget;
   if (S == 0) {
     ctx->have = true;
     if (info_out) *info_out = I;
     return 0;
   }
-  RunOwned own;
-  std::vector<Lap> laps;
-  auto lap_begin = [&](int pass) -> hipError_t {
-    Lap L;
-    L.pass = pass;
-    hipError_t e = own.event(&L.a);
-    if (e == hipSuccess) e = own.event(&L.b);
-    if (e == hipSuccess) e = hipEventRecord(L.a, st);
-    laps.push_back(L);
-    return e;
-  };
-  auto lap_end = [&]() { return hipEventRecord(laps.back().b, st); };
+  Laps T{st};
   DBuf d_off, d_src, d_k, d_tab, d_jobs, d_res, d_pieces, models;
   SyncOnExit sync_on_exit{st};
   // ---- 1: k and the chunk tables
@@ -415,10 +395,10 @@ int decode_batch(spring_unqlfc_ctx *ctx, const std::vector<uint64_t> &coded_off,
   uint32_t stride = PLAN_STRIDE;
   for (int attempt = 0; attempt < 2; attempt++) {   // again with the widest stride where a segment has more chunks
     DALLOC(d_tab, S * stride * 8);
-    HIPCHK(lap_begin(0));
+    HIPCHK(T.begin(0));
     hipLaunchKernelGGL(k_plan, grid(S), dim3(256), 0, st, d_src.as<uint64_t>(), d_off.as<uint64_t>(), (uint32_t)S, stride,
                        d_k.as<uint32_t>(), d_tab.as<int32_t>());
-    HIPCHK(lap_end());
+    HIPCHK(T.end());
     HIPCHK(hipGetLastError());
     HIPCHK(rd(st, h_k.data(), d_k.p, S * 4));
     if (*std::max_element(h_k.begin(), h_k.end()) <= stride) break;
@@ -504,11 +484,11 @@ int decode_batch(spring_unqlfc_ctx *ctx, const std::vector<uint64_t> &coded_off,
       const uint64_t j0 = job0[first[b]], cnt = job0[first[b + 1]] - j0;
       if (!cnt) continue;
       const uint64_t n16 = cnt * (unqlfc::MODEL_BYTES / 16);
-      HIPCHK(lap_begin(1));
+      HIPCHK(T.begin(1));
       hipLaunchKernelGGL(k_fill, grid(n16), dim3(256), 0, st, models.as<uint4>(), n16);
       hipLaunchKernelGGL(k_decode, dim3((unsigned)cnt), dim3(64), 0, st, d_jobs.as<Job>() + j0, models.as<int16_t>(),
                          ctx->rank_tab.as<uint8_t>(), ctx->run_tab.as<uint8_t>(), d_res.as<Res>() + j0);
-      HIPCHK(lap_end());
+      HIPCHK(T.end());
       HIPCHK(hipGetLastError());
     }
     HIPCHK(rd(st, h_res.data(), d_res.p, jobs.size() * sizeof(Res)));
@@ -526,18 +506,13 @@ int decode_batch(spring_unqlfc_ctx *ctx, const std::vector<uint64_t> &coded_off,
   if (!pieces.empty()) {
     DALLOC(d_pieces, pieces.size() * sizeof(Piece));
     HIPCHK(hipMemcpyAsync(d_pieces.p, pieces.data(), pieces.size() * sizeof(Piece), hipMemcpyHostToDevice, st));
-    HIPCHK(lap_begin(2));
+    HIPCHK(T.begin(2));
     hipLaunchKernelGGL(k_copy, dim3((unsigned)pieces.size(), 64), dim3(256), 0, st, d_pieces.as<Piece>());
-    HIPCHK(lap_end());
+    HIPCHK(T.end());
     HIPCHK(hipGetLastError());
   }
   HIPCHK(hipStreamSynchronize(st));   // jobs and pieces are read until here
-  for (const Lap &L : laps) {
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, L.a, L.b));
-    I.ms_pass[L.pass] += ms;
-    I.ms_device += ms;
-  }
+  if (int r = T.collect(I.ms_pass, &I.ms_device)) return r;
   ctx->have = true;
   if (info_out) *info_out = I;
   return 0;

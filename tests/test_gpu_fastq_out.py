@@ -270,6 +270,8 @@ def test_sources_in_hbm_equal_sources_from_the_host(chain):
         for m in range(len(c.f)):
             before = c.ds.download(m), c.qs[m].download(qm.QUALITY), c.qs[m].download(qm.ID)
             (bases, off), (qb, _, qoff), (ib, _, ioff) = before
+            # the decode context's bases have no slack behind them: their last 16-byte word is partial in every case
+            assert len(bases) == int(off[-1]) and len(bases) % 16 != 0, (c.case, m, len(bases))
             for quality in (False, True):
                 fo.assemble(c.ds, c.N, quality=c.qs[m] if quality else None, ids=c.qs[m], paired_end=c.pe,
                             num_reads_per_block=B_CHAIN, mate=m)

@@ -139,6 +139,11 @@ def test_chunk_and_member_edges():
             for data in (pool[:n], b"\x00" * n, bytes(rng.integers(0, 256, n, dtype=np.uint8))):
                 gs.compress(data)
                 check(gs, data, None, ("tiny", n))
+        # a stored chunk whose last bytes lie in the source's partial last word; outputs of 16 k + 12, + 1 and + 15 bytes
+        for n, rest in ((4096 + 5, 12), (4096 + 10, 1), (4096 + 8, 15)):
+            info = gs.compress(pool[:n], mode=0)
+            check(gs, pool[:n], None, ("stored, partial words", n))
+            assert info["chunks_stored"] == 1 and info["bytes_out"] == n + 23 and info["bytes_out"] % 16 == rest
         # members of exactly one byte
         data = pool[:40]
         gs.compress(data, member_off=list(range(41)))

@@ -154,6 +154,27 @@ def test_many_short_lines(which):
             assert d.max() > 1024 and d.min() < 1024
 
 
+@pytest.mark.parametrize("rest", [1, 15])
+def test_outputs_that_end_in_a_partial_word(rest):
+    """Quality and id bytes of 16 k + 1 and 16 k + 15 in all: the copy's last word is written byte by byte, with and
+    without a table."""
+    from spring_amd import QualIdStage
+    lq = (10, 11, 11 + rest)             # 32 + rest quality bytes
+    li = (13, 14, 2 + (16 - rest))       # with their '\n': 48 - rest id bytes, the other remainder
+    f = b"".join(b"@%s\n%s\n+\n%s\n" % (b"i" * (a - 1), b"A" * b, b"I5#"[k:k + 1] * b) for k, (a, b) in enumerate(zip(li, lq)))
+    t, mt = QualIdStage.quality_table("illumina"), qm.illumina_table()
+    with QualIdStage() as qs:
+        qs.set_order([2, 0, 1], 3)
+        slots = qm.order_array(np.array([2, 0, 1], np.uint32), 3, False)
+        for table, model in ((None, None), (t, mt)):
+            info = qs.from_fastq(f, table=table, num_reads_per_block=2)
+            assert info["bytes"] == [32 + rest, 48 - rest]
+            want = qm.from_fastq(f, qm.QUALITY, slots, 2, model)
+            same(qs, qm.QUALITY, want, (rest, table is not None))
+            same(qs, qm.ID, qm.from_fastq(f, qm.ID, slots, 2), (rest, "id"))
+            assert info["bytes_changed"] == (want["changed"] if table is not None else 0)
+
+
 @pytest.mark.parametrize("table", ["none", "illumina", "binary"])
 def test_tables(table):
     from spring_amd import QualIdStage
